@@ -3,6 +3,7 @@
 1440x720x137 float32 grid (BASELINE.json), one process per GPU.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,20 +12,34 @@ ensemble member) that is already resident in HBM.  With N GPUs every rank owns
 one such member (members are independent: no data-path collective, weak
 scaling); `value` = cells processed by all ranks / max-over-ranks wall time.
 
-The JSON line also carries
+A plain run does only what `value` needs: it sets the batch up (placement
+search included), warms up, times the K steps and prints the JSON line, whose
+roofline comes from the HIP events around those K steps.  --dump-outputs DIR
+writes what the last timed step computed, as float32 .npy files (rank 0's
+member): rvort_levels / diverg_levels hold whole levels DUMP_LEVELS, and
+rvort_sample / diverg_sample a fixed, seeded sample of DUMP_SAMPLE cells of
+the whole batch (flat [level][row][column] indices from DUMP_SEED), 42 MB in
+all.  The inputs are generated from a fixed seed, so two builds can be
+compared file for file.
+
+--full adds the checks and side measurements below (each can still be
+switched off on its own with the matching --no-* option):
   verified     : before anything is timed, sampled levels of the GPU's rvort and
                  diverg are compared bit for bit with the reference CPU path (the
                  same calls cpu_baseline times) -- both the ALL_DEFINED fast path
                  and the tested SOME_DEFINED variant; a mismatch aborts the run;
-  roofline     : algorithmic bytes (16 B/cell + map factors once per batch)
-                 over the kernel's average duration measured with HIP events
-                 on the launch stream, against the 8 TB/s HBM3E peak;
+  roofline.per_launch_event_pairs_ms: every launch between its own pair of
+                 HIP events, in a run of its own after the timed steps;
+  roofline_as_allocated: the same launch on four plain allocations;
   check_variant: the same launch with per-cell undefined tests and per-level
                  counts (SOME_DEFINED inputs), timed right after the headline;
   cpu_baseline : the reference CPU path (oracle/_ref, compiled from the
                  reference's own sources; or the bit-exact restatement if that
                  library is not present) calling relvort then divergence per
                  level on this host, on a bounded sample.
+Both kinds of run report `roofline`: algorithmic bytes (16 B/cell + map
+factors once per batch) over the kernel's average duration measured with HIP
+events on the launch stream, against the 8 TB/s HBM3E peak.
 The CPU library is only ever the checker / the reported baseline: nothing inside a
 timed region touches it.
 """
@@ -40,6 +55,9 @@ sys.path.insert(0, ROOT)
 NX, NY, NLEV = 1440, 720, 137
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 SEED = 0x5EED0000 + 3000
+DUMP_LEVELS = (0, NLEV // 2, NLEV - 1)
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 0x5EED0000 + 3001
 
 
 def algorithmic_bytes(nx, ny, nlev):
@@ -202,22 +220,48 @@ def pmc_traffic():
     return None
 
 
+def dump_index(device):
+    """Device indices of what --dump-outputs writes: the levels DUMP_LEVELS, and (level, row, column) of a fixed sample of
+    DUMP_SAMPLE cells.  Made during set-up, so that only device copies follow the steps they copy."""
+    import numpy as np
+    import torch
+
+    flat = np.sort(np.random.default_rng(DUMP_SEED).choice(NLEV * NY * NX, DUMP_SAMPLE, replace=False))
+    cells = tuple(torch.from_numpy(a).to(device) for a in (flat // (NY * NX), flat // NX % NY, flat % NX))
+    return torch.tensor(DUMP_LEVELS, device=device), cells
+
+
+def dump_snapshot(rv, dg, index):
+    """Device copies of the dumped levels and cells of both outputs (stream order keeps later launches from overwriting
+    them first)."""
+    levels, (l, j, i) = index
+    snap = {}
+    for name, t in (("rvort", rv), ("diverg", dg)):
+        snap[name + "_levels"] = t.index_select(0, levels)
+        snap[name + "_sample"] = t[l, j, i]
+    return snap
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20 on one GPU, 100 on several: the max over ranks of a 7.7 ms region is thin)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the comparison with the CPU reference path before timing (profiling runs)")
-    ap.add_argument("--no-check-variant", action="store_true", help="do not time the SOME_DEFINED (per-cell tests + counts) variant")
-    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the tested variant is timed by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify against the CPU reference path, time each launch on its own, the as-allocated batch, the tested variant and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (whole levels and a seeded sample of cells, float32) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: do not time the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the comparison with the CPU reference path before timing (profiling runs)")
+    ap.add_argument("--no-check-variant", action="store_true", help="with --full: do not time the SOME_DEFINED (per-cell tests + counts) variant")
+    ap.add_argument("--check", action="store_true", help="(kept for compatibility: --full times the tested variant)")
     ap.add_argument("--settle-ms", type=float, default=40.0, help="untimed launches for this long before the W warm-up steps (clock ramp after idle); 0 = none")
     ap.add_argument("--placement-pool", type=int, default=48,
                     help="the four arrays of the batch are chosen from a pool of this many arrays allocated in one go (mi-fieldcalc_amd/placement.py: which "
                          "combination of arrays a kernel streams decides its time by up to 12 %%); 0 = four allocations as they come")
     ap.add_argument("--placement-rounds", type=int, default=3, help="pools searched one after the other (each of --placement-pool arrays, --placement-tries probes); the best set is kept")
     ap.add_argument("--placement-tries", type=int, default=240, help="probes (index sets of the pool timed with the kernel) the search may spend; the fastest set is kept")
-    ap.add_argument("--no-as-allocated", action="store_true", help="do not time the same launch on four plain allocations (roofline_as_allocated)")
+    ap.add_argument("--no-as-allocated", action="store_true", help="with --full: do not time the same launch on four plain allocations (roofline_as_allocated)")
     ap.add_argument("--level-stride", type=int, default=None, help="floats between levels (default: the library's mifc_batch_level_stride)")
     args = ap.parse_args()
     if args.steps is None:
@@ -359,7 +403,7 @@ def main():
     # ---- checker leg, before anything is timed: sampled levels against the reference CPU path
     verified, verified_kind = None, None
     sample = (0, NLEV // 2, NLEV - 1)
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         def grab(t):
             return [t[l].cpu().numpy() for l in sample]
 
@@ -378,6 +422,8 @@ def main():
             du[l, 100:110, 200:260] = blk
         verified = True
 
+    dump_at = dump_index(dev) if args.dump_outputs and rank == 0 else None
+
     # The first ~15 ms of GPU work after an idle stretch (the verification above copies levels to the host and
     # runs the CPU reference) run 2-3 % slower (profiles/r02/experiments/time_series.txt): W steps of 0.4 ms do
     # not cover that, so the W warm-up steps are preceded by untimed launches until --settle-ms have passed.
@@ -390,11 +436,14 @@ def main():
         step()
     torch.cuda.synchronize()
     wall, kernel_avg_ms = timed(args.steps)
-    kern_ms = per_launch(max(10, args.steps))
+    kern_ms = per_launch(max(10, args.steps)) if args.full else None
+    # what the last timed step computed: the per-launch pairs of --full repeat that step on the same inputs, so the
+    # copies come after them (the gathers slow the launches that follow them by ~9 %)
+    snapshot = dump_snapshot(rv, dg, dump_at) if dump_at is not None else None
     # the same four-array batch "as allocated": four plain allocations made now, timed like the headline (what a caller who
     # allocates a batch and computes gets; 65-72 % of peak depending on the process)
     as_allocated = None
-    if not args.no_as_allocated and world == 1:
+    if args.full and not args.no_as_allocated and world == 1:
         try:
             keep = (du, dv, rv, dg)
             du, dv, rv, dg = (ctx.batch_empty(NLEV, NY, NX, level_stride=level_stride) for _ in range(4))
@@ -459,12 +508,13 @@ def main():
             "algorithmic_bytes_per_launch": alg,
             "kernel_ms_avg": round(avg_kernel_s * 1e3, 4),
             "kernel_ms_avg_note": "one pair of HIP events around the K launches of the timed region, / K",
-            "per_launch_event_pairs_ms": {"median": round(float(np.median(kern_ms)), 4), "min": round(float(np.min(kern_ms)), 4), "max": round(float(np.max(kern_ms)), 4)},
+            "per_launch_event_pairs_ms": None if kern_ms is None else
+            {"median": round(float(np.median(kern_ms)), 4), "min": round(float(np.min(kern_ms)), 4), "max": round(float(np.max(kern_ms)), 4)},
             "per_rank_frac": per_rank_frac,
         },
         "roofline_as_allocated": as_allocated,
     }
-    if rank == 0 and world == 1 and not args.no_check_variant:
+    if args.full and rank == 0 and world == 1 and not args.no_check_variant:
         du[:, 100:110, 200:260] = float(fc.UNDEF)  # some undefined cells so that the count path does real work
         for _ in range(2):
             step(True)
@@ -485,10 +535,14 @@ def main():
                                 "Mcells_per_s": round(cells_per_step / (chk_ms / 1e3) / 1e6, 1),
                                 "roofline_frac": round(alg / (chk_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                                 "note": "SOME_DEFINED inputs: per-cell undefined tests + per-level counts (memset + kernel), the variant the parity tests cover"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, extras = cpu_baseline()
         out["cpu_baseline"] = base
         out["cpu_baseline_extra"] = extras
+    if snapshot is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in snapshot.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy())
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

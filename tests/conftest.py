@@ -12,6 +12,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
+    # One HIP runtime per process: some CPU tests load libmifc.so with ctypes directly, which would bring in
+    # the system's HIP runtime next to the one torch bundles, and torch would then find no device for the GPU tests
+    # that follow in the same run.  Load torch first, as mi_fieldcalc_amd._capi.load_library does.
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass
     # The CPU checkers are plain gcc builds; make sure they exist (seconds).
     oracle_so = os.path.join(ROOT, "oracle", "libmifc_oracle.so")
     if not os.path.exists(oracle_so) or (

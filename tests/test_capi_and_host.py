@@ -288,16 +288,19 @@ def test_synth_is_deterministic():
 
 def test_cxx_library_exports_the_reference_symbols(built):
     """Binary drop-in: every miutil::fieldcalc / miutil::constants function the compiled
-    reference exports is exported by libmi-fieldcalc.so under the same mangled name."""
-    ref_path = os.path.join(ROOT, "oracle", "_ref", "libmifc_ref.so")
-    if not os.path.exists(ref_path):
-        pytest.skip("compiled reference not available")
+    reference exports (recorded in tests/golden/reference_symbols.txt; where oracle/_ref/
+    holds the compiled reference, the recording must equal what it exports) is exported by
+    libmi-fieldcalc.so under the same mangled name."""
+    import golden_util
 
     def exported(path):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
         return {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
 
-    ref = {s for s in exported(ref_path) if s.startswith("_ZN6miutil")}
+    ref = set(golden_util.reference_symbols())
+    ref_path = os.path.join(ROOT, "oracle", "_ref", "libmifc_ref.so")
+    if os.path.exists(ref_path):
+        assert {s for s in exported(ref_path) if s.startswith("_ZN6miutil")} == ref, "stale tests/golden/reference_symbols.txt"
     mine = exported(CXXLIB)
     # internal helpers the reference happens to export: its OpenMP thread heuristic and a file-local predicate
     internal = {s for s in ref if "compute_num_threads" in s or "bad_hlevel" in s}

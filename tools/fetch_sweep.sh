@@ -10,7 +10,7 @@ for T in "$@"; do
   i=$((i+1))
   D="$OUT/run$i"
   rm -rf "$D"
-  MIFC_VORTDIV_TUNE="$T" rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D" -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline > "$D.log" 2>&1
+  MIFC_VORTDIV_TUNE="$T" rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D" -- python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline > "$D.log" 2>&1
   F=$(find "$D" -name "*counter_collection.csv" | head -1)
   python3 - "$F" "$T" "$D.log" <<'EOF'
 import csv, sys, json

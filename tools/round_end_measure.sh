@@ -10,19 +10,19 @@ export TMPDIR=/tmp
 if [ "$PART" = "b" ]; then
   # the tables of part b are quoted next to a headline number measured in the SAME call, on the same box
   { rocm-smi --showuniqueid 2>/dev/null | grep -i "unique id"; } > "$O/box_tables.txt" 2>&1
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_n1_with_tables.json" 2> "$O/bench_n1_with_tables.err"
+  python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > "$O/bench_n1_with_tables.json" 2> "$O/bench_n1_with_tables.err"
   echo "bench (tables' box) rc=$?"; cat "$O/bench_n1_with_tables.json"
 fi
 if [ "$PART" != "b" ]; then
 # which box: the same binary runs the headline kernel at 66 % on some boxes of the pool and at 73.5 % on others
 { rocm-smi --showuniqueid 2>/dev/null | grep -i "unique id"; echo "HBM vendor: $(cat /sys/class/drm/card*/device/mem_info_vram_vendor 2>/dev/null | head -1)"; echo "vbios: $(cat /sys/class/drm/card*/device/vbios_version 2>/dev/null | head -1)"; } > "$O/box.txt" 2>&1
 cat "$O/box.txt"
-python3 bench.py --steps 20 --warmup 5 > "$O/bench_n1.json" 2> "$O/bench_n1.err"
+python3 bench.py --steps 20 --warmup 5 --full > "$O/bench_n1.json" 2> "$O/bench_n1.err"
 echo "bench rc=$?"; cat "$O/bench_n1.json"
-echo "# five consecutive processes of 'python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline' on ONE box, same binary" > "$O/bench_repeat.txt"
+echo "# five consecutive processes of 'python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline' on ONE box, same binary" > "$O/bench_repeat.txt"
 echo "# Mcells/s  ms_per_step(wall)  kernel_ms_avg(HIP events)  roofline.frac  tested-variant frac (median of 5 bursts)  as-allocated frac  verified  chosen ms per placement pool  tested-variant bursts (ms)" >> "$O/bench_repeat.txt"
 for i in 1 2 3 4 5; do
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms_avg'], d['roofline']['frac'], d.get('check_variant',{}).get('roofline_frac'), (d.get('roofline_as_allocated') or {}).get('frac'), d['verified'], d['config']['placement'].get('rounds_chosen_ms'), d.get('check_variant',{}).get('bursts_ms'))" >> "$O/bench_repeat.txt"
+  python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms_avg'], d['roofline']['frac'], d.get('check_variant',{}).get('roofline_frac'), (d.get('roofline_as_allocated') or {}).get('frac'), d['verified'], d['config']['placement'].get('rounds_chosen_ms'), d.get('check_variant',{}).get('bursts_ms'))" >> "$O/bench_repeat.txt"
 done
 cat "$O/bench_repeat.txt"
 W="K=3,RB=12,LG=6,ZZ=1,D=0"   # the level-walking kernel whose waves load and store (MIFC_VORTDIV_SPLIT=0); the measurement knobs exist for it
