@@ -72,8 +72,9 @@ int mifc_use_own_stream(mifc_ctx* ctx);
 int mifc_synchronize(mifc_ctx* ctx);
 /* Always returns 0 and leaves "<what>: not built on the GPU (...)" in mifc_last_error(): what the
  * source-compatible C++ API calls for the reference functions outside the hot-path scope
- * (neighbourFunctions, neighbourProbFunctions, vesselIcingModStall, vesselIcingMincog), so that
- * their `false` can be told from an argument-validation failure. */
+ * (vesselIcingModStall, vesselIcingMincog, and -- until its forwarding line is switched to
+ * mifc_neighbourFunctions -- neighbourFunctions), so that their `false` can be told from an
+ * argument-validation failure. */
 int mifc_not_built(mifc_ctx* ctx, const char* what);
 /* The library's tuning / diagnostic environment variables (MIFC_*: which of several
  * equivalent kernel forms runs; none changes a result) are read when a context is
@@ -296,6 +297,34 @@ int mifc_extremeValue(mifc_ctx* ctx, int compute, int nx, int ny, const float* c
                       int memkind);
 int mifc_probability(mifc_ctx* ctx, int compute, int nx, int ny, const float* const* fields, const int* fdefined_in, int nfields,
                      const float* limits, int nlimits, float* fres, int* fdefined_out, float undef, int memkind);
+
+/* ---- neighbourhood statistics ----------------------------------------------
+ * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
+ * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int
+ * (prob: limit = c[0], range = c[1]; functions, compute < 4: range = c[0], step = c[1] only when
+ * nconstants == 2, else 3; compute >= 4: limit = c[0], range = c[1], step = c[2] only when nconstants == 3);
+ * the field is compared against (float)limit.  `constants` is always a HOST array.
+ *   neighbourProbFunctions: 0/1 per cell (compute 5: field > limit, 6: field < limit); range 0 returns that
+ *     field with the flag unchanged (and writes nothing for another compute); otherwise the (2r+1)^2 box
+ *     count / N, cells closer than r to the edge undef, flag SOME_DEFINED.  field == fres is allowed.  The
+ *     count is exact; the reference's float summed-area table is only while nx * ny <= 2^24.
+ *   neighbourFunctions: undef border, then each centre (r, r + step, ... < n - r) writes its value --
+ *     compute 1 mean, 2 max, 3 min, 4 percentile c[0], 5 / 6 fraction above / below limit, else +0 -- into
+ *     its step x step block; interior cells no block covers keep the caller's content (host memory too).
+ * Refused (0, nothing written, mifc_last_error() says why) where the reference is undefined: prob with
+ * range < 0 or > nx / ny, prob with compute not 5 / 6 and range > 0, functions with step / 2 > range,
+ * a percentile index outside the window, functions with field == fres, a NaN or out-of-int-range constant
+ * ("Neighbourhood statistics").  The reference's own `false` leaves mifc_last_error() empty. */
+int mifc_neighbourProbFunctions(mifc_ctx* ctx, int nx, int ny, const float* field, const float* constants, int nconstants, int compute,
+                                float* fres, int* fdefined, float undef, int memkind);
+int mifc_neighbourFunctions(mifc_ctx* ctx, int nx, int ny, const float* field, const float* constants, int nconstants, int compute,
+                            float* fres, int* fdefined, float undef, int memkind);
+/* Either function over a [nlev][ny][nx] batch in one launch, the scalars shared: `which` is MIFC_NEIGHBOUR_PROB or
+ * MIFC_NEIGHBOUR_FUNCTIONS, fdefined[nlev] in/out.  Returns 0 and writes nothing if any level's flag is not
+ * ALL_DEFINED. */
+enum { MIFC_NEIGHBOUR_PROB = 0, MIFC_NEIGHBOUR_FUNCTIONS = 1 };
+int mifc_neighbour_levels(mifc_ctx* ctx, int which, int compute, int nx, int ny, int nlev, const float* field, const float* constants,
+                          int nconstants, float* fres, int* fdefined, float undef, int memkind);
 
 /* ---- batched over vertical levels / ensemble members (new surface) ------ */
 /* The reference is called once per 2-D field; a caller that wants vorticity

@@ -514,6 +514,53 @@ class Context:
         lim = np.ascontiguousarray(limits, dtype=np.float32)
         return self._ensemble("mifc_probability", fields, fdefined_in, [int(compute)], [lim.ctypes.data, int(lim.size)], fdefined, undef, out)
 
+    # ------------------------------------------------------ neighbourhood statistics
+    # out=None allocates an output pre-filled with `undef`: the reference leaves some cells unwritten (neighbourFunctions:
+    # interior cells that no step x step block covers; neighbourProbFunctions with range 0 and a compute other than 5 / 6:
+    # every cell), and these come back as `undef` instead of uninitialised memory.  With out= given they keep its values.
+    # Refusals where the reference is undefined raise RuntimeError with the reason (include/mifc.h); the reference's
+    # own `false` gives None.
+    def _neighbour(self, name, field, constants, compute, fdefined, undef, out):
+        if out is None:
+            out = _empty_like(field)
+            out[...] = float(np.float32(undef))
+        consts = np.ascontiguousarray(constants, dtype=np.float32).ravel()
+        return self._single(name, [field], [consts.ctypes.data, int(consts.size), int(compute)], [out], fdefined, undef)
+
+    def neighbourProbFunctions(self, field, constants, compute, fdefined=ALL_DEFINED, undef=UNDEF, out=None):
+        """constants = [limit, range]; compute 5: fraction of the (2r+1)^2 box above limit, 6: below.  out=field works in place."""
+        return self._neighbour("mifc_neighbourProbFunctions", field, constants, compute, fdefined, undef, out)
+
+    def neighbourFunctions(self, field, constants, compute, fdefined=ALL_DEFINED, undef=UNDEF, out=None):
+        """compute 1 mean, 2 max, 3 min (constants = [range(, step)]), 4 percentile, 5 / 6 fraction above / below
+        (constants = [percentile or limit, range(, step)]); each computed centre fills its step x step block."""
+        return self._neighbour("mifc_neighbourFunctions", field, constants, compute, fdefined, undef, out)
+
+    def neighbour_levels(self, which, compute, field, constants, fdefined=None, undef=UNDEF, out=None):
+        """Either function over a (nlev, ny, nx) batch in one launch.  which: "prob" (neighbourProbFunctions) or
+        "functions".  fdefined: per-level flags (default ALL_DEFINED).  Returns (out, flags ndarray) or None."""
+        codes = {"prob": 0, "functions": 1}
+        if which not in codes:
+            raise ValueError("which must be 'prob' or 'functions'")
+        fa = _Arg(field)
+        if len(fa.shape) != 3:
+            raise ValueError("field must have shape (nlev, ny, nx)")
+        nlev, ny, nx = fa.shape
+        if out is None:
+            out = _empty_like(field)
+            out[...] = float(np.float32(undef))
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != tuple(fa.shape):
+            raise ValueError("out must have the shape of field")
+        mk = _memkind([fa, oa], self.device)
+        self._bind_stream(mk)
+        flags = np.full(nlev, ALL_DEFINED, np.int32) if fdefined is None else np.array(fdefined, dtype=np.int32).reshape(nlev).copy()
+        consts = np.ascontiguousarray(constants, dtype=np.float32).ravel()
+        if not self._call("mifc_neighbour_levels", [codes[which], int(compute), nx, ny, nlev, fa.addr, consts.ctypes.data, int(consts.size),
+                                                     oa.addr, flags, float(undef), mk]):
+            return None
+        return (out if _is_torch(out) else oa.keep), flags
+
     # ------------------------------------------------------------------ batched
     def vortdiv_levels(self, u, v, xmapr, ymapr, fdefined=None, undef=UNDEF, rvort=None, diverg=None, want=("rvort", "diverg")):
         """Fused relvort + divergence over u, v of shape (nlev, ny, nx).

@@ -122,6 +122,10 @@ SIGNATURES = {
     "mifc_stddevValue": ("i", ["ctx", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_extremeValue": ("i", ["ctx", "i", "i", "i", "p", "i", "p", "pi", "f", "i"]),
     "mifc_probability": ("i", ["ctx", "i", "i", "i", "p", "p", "i", "p", "i", "p", "pi", "f", "i"]),
+    # neighbourhood statistics (constants: host float array)
+    "mifc_neighbourProbFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_neighbourFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_neighbour_levels": ("i", ["ctx", "i", "i", "i", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     # batched
     "mifc_vortdiv_levels": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
     "mifc_stencil_levels": ("i", ["ctx", "i", "i", "i", "i", "p", "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),

@@ -338,6 +338,35 @@ struct Fused2Params
 bool fused2_supported(const Fused2Params& prm);
 hipError_t launch_fused2(const Fused2Params& prm, hipStream_t stream);
 
+// ---------------------------------------------------------------- neighbourhood statistics
+// neighbourProbFunctions :2862 / neighbourFunctions :2955 (mifc_neighbour.hip).  [nlev][ny][nx] batches, level_stride
+// floats apart; the host has validated every scalar (range >= 1 except the range-0 threshold, step / 2 <= range,
+// 0 <= ii < N), so every write lands inside the level.
+struct NeighbourParams
+{
+  int nx, ny, nlev;
+  long level_stride;
+  int compute;  // 1 mean, 2 max, 3 min, 4 percentile, 5 count >, 6 count <; anything else writes +0 into its blocks
+  int range, step;
+  float limit;  // (float)(int)constant, as the reference compares float field against int limit
+  float nf;     // (float)(2r+1)^2
+  int ii;       // percentile index, 0 <= ii < N
+  float undef;
+  const float* in;
+  float* out;
+  u64* bits; // box counts: [nlev][ny][nwords] threshold bit rows (nwords = ceil(nx / 64))
+};
+__host__ __device__ inline int neighbour_words(int nx)
+{
+  return (nx + 63) / 64;
+}
+// compute 5/6 per cell as 0/1 (neighbourProbFunctions with range 0)
+hipError_t launch_neighbour_threshold(const NeighbourParams& P, hipStream_t stream);
+// compute 5/6 box count of every cell / (float)N, border undef: neighbourProbFunctions, and neighbourFunctions with step 1
+hipError_t launch_neighbour_box(const NeighbourParams& P, hipStream_t stream);
+// neighbourFunctions: undef border, then every centre's step x step block
+hipError_t launch_neighbour_functions(const NeighbourParams& P, hipStream_t stream);
+
 #ifdef MIFC_MEASUREMENT_BUILD // libmifc_measure.so only
 // diagnostic: (0.5*a*b*g0)/g through the shared-reciprocal quotient of mifc_device.h and through a plain f64 division
 hipError_t launch_division_check(const float* a, const float* b, const float* g, float* shared, float* plain, size_t n, hipStream_t stream);

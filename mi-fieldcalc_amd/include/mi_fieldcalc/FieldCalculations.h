@@ -13,9 +13,9 @@
 //
 // Every function the reference header declares is declared here and exported
 // by libmi-fieldcalc.so with the same mangled name, so existing callers compile
-// and link unchanged.  Four of them are not built on the GPU and return false
+// and link unchanged.  Three of them are not built on the GPU and return false
 // (they never compute on the CPU): vesselIcingModStall, vesselIcingMincog,
-// neighbourProbFunctions, neighbourFunctions.
+// neighbourFunctions (its GPU form is mifc_neighbourFunctions of the C ABI).
 #ifndef MI_FIELDCALC_FIELDCALCULATIONS_H
 #define MI_FIELDCALC_FIELDCALCULATIONS_H
 
@@ -189,8 +189,8 @@ bool extremeValue(int compute, int nx, int ny, const std::vector<float*>& fields
 bool probability(int compute, int nx, int ny, const std::vector<float*>& fields, const std::vector<ValuesDefined>& fDefinedIn,
                  const std::vector<float>& limits, float* fres, ValuesDefined& fDefinedOut, float undef);
 
-// Neighbourhood statistics: declared for link compatibility, not built on the GPU
-// (outside the accelerated path); they return false and do not compute on the CPU.
+// Neighbourhood statistics: neighbourProbFunctions runs on the GPU (include/mifc.h); neighbourFunctions
+// is declared for link compatibility and still returns false with "not built" in last_error().
 bool neighbourProbFunctions(int nx, int ny, const float* field, const std::vector<float>& constants, int compute,
                             float* fres, ValuesDefined& fDefined, float undef);
 bool neighbourFunctions(int nx, int ny, const float* field, const std::vector<float>& constants, int compute,

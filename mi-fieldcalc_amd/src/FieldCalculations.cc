@@ -351,9 +351,11 @@ bool vesselIcingMincog(int, int, const float*, const float*, const float*, const
   return mifc_not_built(context(), "vesselIcingMincog") != 0;
 }
 
-bool neighbourProbFunctions(int, int, const float*, const std::vector<float>&, int, float*, ValuesDefined&, float)
+bool neighbourProbFunctions(int nx, int ny, const float* field, const std::vector<float>& constants, int compute, float* fres,
+                            ValuesDefined& fDefined, float undef)
 {
-  return mifc_not_built(context(), "neighbourProbFunctions") != 0; // FieldCalculations.cc:2862
+  MIFC_FORWARD(mifc_neighbourProbFunctions(context(), nx, ny, field, constants.data(), static_cast<int>(constants.size()), compute, fres, f.ptr(), undef,
+                                           MIFC_MEM_HOST));
 }
 bool neighbourFunctions(int, int, const float*, const std::vector<float>&, int, float*, ValuesDefined&, float)
 {
