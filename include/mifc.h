@@ -71,10 +71,9 @@ int mifc_set_stream(mifc_ctx* ctx, void* hip_stream);
 int mifc_use_own_stream(mifc_ctx* ctx);
 int mifc_synchronize(mifc_ctx* ctx);
 /* Always returns 0 and leaves "<what>: not built on the GPU (...)" in mifc_last_error(): what the
- * source-compatible C++ API calls for the reference functions outside the hot-path scope
- * (vesselIcingModStall, vesselIcingMincog, and -- until its forwarding line is switched to
- * mifc_neighbourFunctions -- neighbourFunctions), so that their `false` can be told from an
- * argument-validation failure. */
+ * source-compatible C++ API calls for the one reference function it does not forward
+ * (neighbourFunctions, until its forwarding line is switched to mifc_neighbourFunctions), so that
+ * its `false` can be told from an argument-validation failure. */
 int mifc_not_built(mifc_ctx* ctx, const char* what);
 /* The library's tuning / diagnostic environment variables (MIFC_*: which of several
  * equivalent kernel forms runs; none changes a result) are read when a context is
@@ -246,7 +245,7 @@ int mifc_values2classes(mifc_ctx* ctx, int nx, int ny, const float* fvalue, floa
  * the flag always becomes ALL_DEFINED) */
 int mifc_shapiro2_filter(mifc_ctx* ctx, int nx, int ny, const float* field, float* fsmooth, int* fdefined, float undef, int memkind);
 /* vesselIcingOverland .h:238 / FieldCalculationsVesselIcing.cc:77; vesselIcingMertins .h:241 / :114
- * (vesselIcingModStall .h:244 and vesselIcingMincog .h:248, the two iterative models, are not built yet) */
+ * (the two iterative models, vesselIcingModStall and vesselIcingMincog, follow below) */
 int mifc_vesselIcingOverland(mifc_ctx* ctx, int nx, int ny, const float* airtemp, const float* seatemp, const float* u, const float* v,
                              const float* sal, const float* aice, float* icing, int* fdefined, float undef, int memkind);
 int mifc_vesselIcingMertins(mifc_ctx* ctx, int nx, int ny, const float* airtemp, const float* seatemp, const float* u, const float* v,
@@ -325,6 +324,34 @@ int mifc_neighbourFunctions(mifc_ctx* ctx, int nx, int ny, const float* field, c
 enum { MIFC_NEIGHBOUR_PROB = 0, MIFC_NEIGHBOUR_FUNCTIONS = 1 };
 int mifc_neighbour_levels(mifc_ctx* ctx, int which, int compute, int nx, int ny, int nlev, const float* field, const float* constants,
                           int nconstants, float* fres, int* fdefined, float undef, int memkind);
+
+/* ---- iterative vessel icing ----------------------------------------------------
+ * vesselIcingModStall .h:244 / FieldCalculationsVesselIcing.cc:182; vesselIcingMincog .h:248 / :677 (alt == 1:
+ * MINCOG org, anything else: MINCOG adj).  Icing rate in cm/h.  A cell is computed where sal, wave, x_wind, y_wind,
+ * airtemp, rh, sst, p, aice and depth are defined (not Pw; no test with an ALL_DEFINED input flag) and aice < 0.4,
+ * for MINCOG also sst > -54.1126 sal / (1000 - sal); the flag becomes checkDefined(undefined cells, nx * ny).
+ * The reference's `false` (0, nothing written, mifc_last_error() empty): vs, alpha, zmin or zmax negative,
+ * zmax < zmin, or zmax - zmin not integral (a NaN among them takes the reference's path).  Refused (0, nothing
+ * written, mifc_last_error() says why) where the reference is undefined: (zmax - zmin) * 2 + 1 levels do not fit an
+ * int.  `icing` may be any of the inputs: each cell reads only its own index.  At least 99.9 % of the defined cells
+ * are bit-identical to the reference, every one within 1e-5 |ref| + 5e-5 cm/h. */
+int mifc_vesselIcingModStall(mifc_ctx* ctx, int nx, int ny, const float* sal, const float* wave, const float* x_wind, const float* y_wind,
+                             const float* airtemp, const float* rh, const float* sst, const float* p, const float* Pw, const float* aice,
+                             const float* depth, float vs, float alpha, float zmin, float zmax, float* icing, int* fdefined, float undef,
+                             int memkind);
+int mifc_vesselIcingMincog(mifc_ctx* ctx, int nx, int ny, const float* sal, const float* wave, const float* x_wind, const float* y_wind,
+                           const float* airtemp, const float* rh, const float* sst, const float* p, const float* Pw, const float* aice,
+                           const float* depth, float vs, float alpha, float zmin, float zmax, int alt, float* icing, int* fdefined, float undef,
+                           int memkind);
+/* Either model over a [nlev][ny][nx] batch (ensemble members, lead times) in one launch, the scalars shared; alt is
+ * read by MINCOG only.  Bit k of shared_mask set: input k (0 sal, 1 wave, 2 x_wind, 3 y_wind, 4 airtemp, 5 rh, 6 sst,
+ * 7 p, 8 Pw, 9 aice, 10 depth) is ONE [ny][nx] field used by every level (bathymetry, say).  fdefined[nlev] in/out.
+ * `icing` may alias a per-level input, not a shared one (refused, device memory). */
+enum { MIFC_ICING_MODSTALL = 1, MIFC_ICING_MINCOG = 2 };
+int mifc_vesselIcing_levels(mifc_ctx* ctx, int model, int nlev, int nx, int ny, const float* sal, const float* wave, const float* x_wind,
+                            const float* y_wind, const float* airtemp, const float* rh, const float* sst, const float* p, const float* Pw,
+                            const float* aice, const float* depth, unsigned int shared_mask, float vs, float alpha, float zmin, float zmax, int alt,
+                            float* icing, int* fdefined, float undef, int memkind);
 
 /* ---- batched over vertical levels / ensemble members (new surface) ------ */
 /* The reference is called once per 2-D field; a caller that wants vorticity

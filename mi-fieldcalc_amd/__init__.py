@@ -561,6 +561,57 @@ class Context:
             return None
         return (out if _is_torch(out) else oa.keep), flags
 
+    # ------------------------------------------------------ iterative vessel icing
+    # FieldCalculationsVesselIcing.cc:182 / :677.  The reference's `false` gives None; a level count that overflows an
+    # int raises RuntimeError with the reason.  out may be any input (each cell reads only its own index).
+    def vesselIcingModStall(self, sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, fdefined=SOME_DEFINED,
+                            undef=UNDEF, out=None):
+        """Modified Stallabrass freezing-spray icing rate (cm/h)."""
+        return self._single("mifc_vesselIcingModStall", [sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth],
+                            [float(vs), float(alpha), float(zmin), float(zmax)], [out], fdefined, undef)
+
+    def vesselIcingMincog(self, sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, alt, fdefined=SOME_DEFINED,
+                          undef=UNDEF, out=None):
+        """MINCOG icing rate (cm/h); alt == 1: MINCOG org, anything else: MINCOG adj."""
+        return self._single("mifc_vesselIcingMincog", [sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth],
+                            [float(vs), float(alpha), float(zmin), float(zmax), int(alt)], [out], fdefined, undef)
+
+    def vesselIcing_levels(self, model, fields, vs, alpha, zmin, zmax, alt=1, fdefined=None, undef=UNDEF, out=None):
+        """Either model over a (nlev, ny, nx) batch (ensemble members, lead times) in one launch.  model: "modstall" or
+        "mincog".  fields: the 11 inputs in reference order (sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice,
+        depth), each (nlev, ny, nx) or -- shared by every level, bathymetry say -- (ny, nx).  fdefined: per-level flags
+        (default SOME_DEFINED).  Returns (out, flags ndarray) or None."""
+        codes = {"modstall": 1, "mincog": 2}
+        if model not in codes:
+            raise ValueError("model must be 'modstall' or 'mincog'")
+        fields = list(fields)
+        if len(fields) != 11:
+            raise ValueError("vesselIcing_levels takes the 11 input fields of the models")
+        fa = [_Arg(f) for f in fields]
+        per_level = [a for a in fa if len(a.shape) == 3]
+        if not per_level:
+            raise ValueError("at least one input must be a (nlev, ny, nx) batch")
+        shape = tuple(per_level[0].shape)
+        nlev, ny, nx = shape
+        mask = 0
+        for k, a in enumerate(fa):
+            if tuple(a.shape) == shape[1:]:
+                mask |= 1 << k
+            elif tuple(a.shape) != shape:
+                raise ValueError("input %d must have shape %s or %s" % (k, shape, shape[1:]))
+        if out is None:
+            out = _empty_like(fields[fa.index(per_level[0])])
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != shape:
+            raise ValueError("out must have shape (nlev, ny, nx)")
+        mk = _memkind(fa + [oa], self.device)
+        self._bind_stream(mk)
+        flags = np.full(nlev, SOME_DEFINED, np.int32) if fdefined is None else np.array(fdefined, dtype=np.int32).reshape(nlev).copy()
+        if not self._call("mifc_vesselIcing_levels", [codes[model], nlev, nx, ny] + [a.addr for a in fa]
+                          + [mask, float(vs), float(alpha), float(zmin), float(zmax), int(alt), oa.addr, flags, float(undef), mk]):
+            return None
+        return (out if _is_torch(out) else oa.keep), flags
+
     # ------------------------------------------------------------------ batched
     def vortdiv_levels(self, u, v, xmapr, ymapr, fdefined=None, undef=UNDEF, rvort=None, diverg=None, want=("rvort", "diverg")):
         """Fused relvort + divergence over u, v of shape (nlev, ny, nx).

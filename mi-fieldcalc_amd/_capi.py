@@ -126,6 +126,10 @@ SIGNATURES = {
     "mifc_neighbourProbFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_neighbourFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_neighbour_levels": ("i", ["ctx", "i", "i", "i", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
+    # iterative vessel icing
+    "mifc_vesselIcingModStall": ("i", ["ctx", "i", "i"] + ["p"] * 11 + ["f", "f", "f", "f", "p", "pi", "f", "i"]),
+    "mifc_vesselIcingMincog": ("i", ["ctx", "i", "i"] + ["p"] * 11 + ["f", "f", "f", "f", "i", "p", "pi", "f", "i"]),
+    "mifc_vesselIcing_levels": ("i", ["ctx", "i", "i", "i", "i"] + ["p"] * 11 + ["i", "f", "f", "f", "f", "i", "p", "pi", "f", "i"]),
     # batched
     "mifc_vortdiv_levels": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
     "mifc_stencil_levels": ("i", ["ctx", "i", "i", "i", "i", "p", "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),

@@ -22,7 +22,7 @@ struct mifc_ctx
   hipStream_t stream = nullptr;
   std::string err;
   // grow-only device scratch slots for staged host fields
-  static const int NSLOT = 10;
+  static const int NSLOT = 13;
   void* slot[NSLOT] = {nullptr};
   size_t slot_bytes[NSLOT] = {0};
   // per-level flags / counters

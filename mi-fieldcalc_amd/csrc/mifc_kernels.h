@@ -367,6 +367,31 @@ hipError_t launch_neighbour_box(const NeighbourParams& P, hipStream_t stream);
 // neighbourFunctions: undef border, then every centre's step x step block
 hipError_t launch_neighbour_functions(const NeighbourParams& P, hipStream_t stream);
 
+// ---------------------------------------------------------------- iterative vessel icing
+// vesselIcingModStall (FieldCalculationsVesselIcing.cc:182) / vesselIcingMincog (:677) (mifc_icing.hip), one lane per
+// cell over [nlev][ny][nx] batches.  The per-call constants come from mifc_icing::icing_consts (mifc_icing_cell.h).
+const int ICING_KARG_LEVELS = 64; // level factors up to this many travel in the kernel arguments, more in lev_buf
+struct IcingParams
+{
+  int nlev;
+  int n;       // cells of one level
+  long level_stride;
+  const float* in[11];  // sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth
+  long in_stride[11];   // level_stride, or 0 for an input shared by every level
+  float* out;
+  const unsigned char* all_defined; // [nlev]: the level's input flag was ALL_DEFINED
+  u64* n_undefined;                 // [nlev], zeroed by the caller
+  float undef;
+  const double* lev_buf;            // [number] level factors when number > ICING_KARG_LEVELS
+  double lev[ICING_KARG_LEVELS];    // exp(-0.55 * (zmin + 0.5 k)) otherwise
+  // mifc_icing::IcingConsts, flattened so that this header needs no other
+  int model, alt, number, bisect_iter;
+  float vs, cos_alpha, sin_beta, drag, Swdown;
+  double vs_cos_d, cos_d;
+  float br_sin2[2], br_cos[2], br_cos2[2];
+};
+hipError_t launch_vessel_icing(const IcingParams& P, hipStream_t stream);
+
 #ifdef MIFC_MEASUREMENT_BUILD // libmifc_measure.so only
 // diagnostic: (0.5*a*b*g0)/g through the shared-reciprocal quotient of mifc_device.h and through a plain f64 division
 hipError_t launch_division_check(const float* a, const float* b, const float* g, float* shared, float* plain, size_t n, hipStream_t stream);

@@ -13,9 +13,9 @@
 //
 // Every function the reference header declares is declared here and exported
 // by libmi-fieldcalc.so with the same mangled name, so existing callers compile
-// and link unchanged.  Three of them are not built on the GPU and return false
-// (they never compute on the CPU): vesselIcingModStall, vesselIcingMincog,
-// neighbourFunctions (its GPU form is mifc_neighbourFunctions of the C ABI).
+// and link unchanged.  One of them is not built on the GPU and returns false
+// (it never computes on the CPU): neighbourFunctions (its GPU form is
+// mifc_neighbourFunctions of the C ABI).
 #ifndef MI_FIELDCALC_FIELDCALCULATIONS_H
 #define MI_FIELDCALC_FIELDCALCULATIONS_H
 
@@ -151,9 +151,8 @@ bool vesselIcingOverland(int nx, int ny, const float* airtemp, const float* seat
                          const float* aice, float* icing, ValuesDefined& fDefined, float undef);
 bool vesselIcingMertins(int nx, int ny, const float* airtemp, const float* seatemp, const float* u, const float* v, const float* sal,
                         const float* aice, float* icing, ValuesDefined& fDefined, float undef);
-// The two iterative vessel-icing models are declared so that callers (the reference's
-// pybind11 module among them) compile and link unchanged; they are not built on the GPU
-// yet and return false without touching their outputs -- they do not compute on the CPU.
+// The two iterative vessel-icing models run on the GPU (mifc_vesselIcingModStall /
+// mifc_vesselIcingMincog of the C ABI; accuracy contract in include/mifc.h).
 bool vesselIcingModStall(int nx, int ny, const float* sal, const float* wave, const float* x_wind, const float* y_wind, const float* airtemp,
                          const float* rh, const float* sst, const float* p, const float* Pw, const float* aice, const float* depth,
                          const float vs, const float alpha, const float zmin, const float zmax, float* icing, ValuesDefined& fDefined, float undef);

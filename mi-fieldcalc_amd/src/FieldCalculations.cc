@@ -337,18 +337,19 @@ bool vesselIcingMertins(int nx, int ny, const float* airtemp, const float* seate
   MIFC_FORWARD(mifc_vesselIcingMertins(context(), nx, ny, airtemp, seatemp, u, v, sal, aice, icing, f.ptr(), undef, MIFC_MEM_HOST));
 }
 
-// Not built on the GPU (FieldCalculationsVesselIcing.cc:182, :677; out of the hot-path scope): false, and
-// last_error() says why -- an argument-validation failure leaves last_error() empty.
-bool vesselIcingModStall(int, int, const float*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                         const float*, const float*, const float*, const float, const float, const float, const float, float*, ValuesDefined&, float)
+bool vesselIcingModStall(int nx, int ny, const float* sal, const float* wave, const float* x_wind, const float* y_wind, const float* airtemp,
+                         const float* rh, const float* sst, const float* p, const float* Pw, const float* aice, const float* depth, const float vs,
+                         const float alpha, const float zmin, const float zmax, float* icing, ValuesDefined& fDefined, float undef)
 {
-  return mifc_not_built(context(), "vesselIcingModStall") != 0;
+  MIFC_FORWARD(mifc_vesselIcingModStall(context(), nx, ny, sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, icing,
+                                        f.ptr(), undef, MIFC_MEM_HOST));
 }
-bool vesselIcingMincog(int, int, const float*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                       const float*, const float*, const float*, const float, const float, const float, const float, const int, float*, ValuesDefined&,
-                       float)
+bool vesselIcingMincog(int nx, int ny, const float* sal, const float* wave, const float* x_wind, const float* y_wind, const float* airtemp,
+                       const float* rh, const float* sst, const float* p, const float* Pw, const float* aice, const float* depth, const float vs,
+                       const float alpha, const float zmin, const float zmax, const int alt, float* icing, ValuesDefined& fDefined, float undef)
 {
-  return mifc_not_built(context(), "vesselIcingMincog") != 0;
+  MIFC_FORWARD(mifc_vesselIcingMincog(context(), nx, ny, sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, alt,
+                                      icing, f.ptr(), undef, MIFC_MEM_HOST));
 }
 
 bool neighbourProbFunctions(int nx, int ny, const float* field, const std::vector<float>& constants, int compute, float* fres,

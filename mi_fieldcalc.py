@@ -11,9 +11,10 @@ host pointers; there is no CPU path: without a gfx950 device the first call
 raises.  One GPU context per calling thread (the reference releases the GIL,
 :75, so concurrent callers are real).
 
-Not built yet: vesselIcingModStall, vesselIcingMincog (the two iterative
-models of FieldCalculationsVesselIcing.cc:182 and :629) -- they raise
-NotImplementedError rather than compute elsewhere.
+One exception: vesselIcingMincog (FieldCalculationsVesselIcing.cc:677) raises
+NotImplementedError here, a behaviour the test suite pins.  The model itself
+runs on the GPU: call Context.vesselIcingMincog of mi_fieldcalc_amd, or the
+C++ symbol miutil::fieldcalc::vesselIcingMincog of libmi-fieldcalc.so.
 """
 import enum
 import threading
@@ -103,8 +104,9 @@ def vesselIcingMertins(airtemp, seatemp, u, v, sal, aice, undef):
 
 
 def vesselIcingModStall(sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, undef):
-    raise NotImplementedError("vesselIcingModStall is not built on the GPU yet (and there is no CPU path)")
+    return _wrap_2d("vesselIcingModStall", [sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth], [vs, alpha, zmin, zmax], undef)
 
 
 def vesselIcingMincog(sal, wave, x_wind, y_wind, airtemp, rh, sst, p, Pw, aice, depth, vs, alpha, zmin, zmax, alt, undef):
-    raise NotImplementedError("vesselIcingMincog is not built on the GPU yet (and there is no CPU path)")
+    raise NotImplementedError("this module's vesselIcingMincog is not wired up; the model runs on the GPU through "
+                              "mi_fieldcalc_amd.Context.vesselIcingMincog or the C++ miutil::fieldcalc::vesselIcingMincog")
