@@ -297,6 +297,44 @@ int mifc_extremeValue(mifc_ctx* ctx, int compute, int nx, int ny, const float* c
 int mifc_probability(mifc_ctx* ctx, int compute, int nx, int ny, const float* const* fields, const int* fdefined_in, int nfields,
                      const float* limits, int nlimits, float* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: percentiles across ensemble members ---------------------------------------------------------
+ * Not a miutil::fieldcalc function; the reference's rule for choosing a percentile is neighbourFunctions compute 4
+ * (FieldCalculations.cc:2955-3061).  Inputs are nmem members.  Each member is a [nlev][ny][nx] float field, with one
+ * input flag per member and level.  For each level l and cell i:
+ *   1. Defined members.  Member j counts at (l, i) under exactly meanValue's rule (FieldCalculations.cc:2710):
+ *      is_defined(flag[j][l] == ALL_DEFINED, x, undef).  A member flagged ALL_DEFINED is taken at its word.  Let n be
+ *      the number of members that count.
+ *   2. If n == 0, every output at that cell is undef.
+ *   3. Order.  The counted values are sorted ascending in IEEE total order: -inf < ... < -0 < +0 < ... < +inf.  Every
+ *      NaN (which can only reach the sort through an ALL_DEFINED member) sorts above +inf, and the result is then some
+ *      NaN (payload free).  The order is independent of member order, so the result does not depend on which member
+ *      holds which value.
+ *   4. Percentile p is a float in [0, 100].  The two methods are:
+ *      * MIFC_QUANTILE_LOWER = 0, the reference's neighbourFunctions rule.  ii = (int)(((float)n * p) / 100.0f), all
+ *        in float, truncated.  It is clamped to n - 1, so p = 100 gives the maximum instead of the reference's
+ *        out-of-range read.  The result is x[ii], the stored value bit for bit.
+ *      * MIFC_QUANTILE_LINEAR = 1, numpy's default "linear" method (Hyndman-Fan type 7) with fixed arithmetic.  All
+ *        steps are in double, each rounded, with no contraction: h = ((double)(n - 1) * (double)p) / 100.0,
+ *        k = (int)h, t = h - k.  If t == 0 the result is x[k] bit for bit.  Otherwise it is
+ *        (float)(x[k] + t * (x[k+1] - x[k])), with both x values widened to double.
+ *   5. Output flags.  fdefined_out[l] = checkDefined(#cells with n == 0, nx*ny).  This is by construction the flag
+ *      meanValue returns on the same level and member flags.
+ * Special cases:
+ *   * nmem == 0 behaves like meanValue with no fields: all outputs undef, flags NONE_DEFINED, return 1.
+ *   * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: an unknown method;
+ *     nq < 1; a p that is NaN or outside [0, 100]; nlev < 1, or a negative nx, ny or nmem; a null pointer; two outputs
+ *     that are the same array (or overlap); a call made while a mifc_graph capture is open.
+ *   * An output may be exactly one of the member arrays (in-place).  Each cell reads only its own index.
+ * Arguments follow the ensemble reductions above: `fields` is a HOST array of nmem pointers, each pointing to
+ * [nlev][ny][nx]; `fdefined_in` a HOST int[nmem * nlev], member-major (j * nlev + l), NULL = all SOME_DEFINED;
+ * `percentiles` a HOST float[nq]; `fres` a HOST array of nq output pointers, each pointing to [nlev][ny][nx];
+ * `fdefined_out` a HOST int[nlev].  memkind works as everywhere else; host memory works at any size: the call stages a
+ * bounded chunk of levels (or of one level's cells) at a time, MIFC_QUANTILE_CHUNK_MIB of device memory (default 256).
+ * Sorting network in registers up to 64 members, an exact bisection over the keys above. */
+enum { MIFC_QUANTILE_LOWER = 0, MIFC_QUANTILE_LINEAR = 1 };
+int mifc_ensembleQuantiles(mifc_ctx* ctx, int method, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nmem,
+                           const float* percentiles, int nq, float* const* fres, int* fdefined_out, float undef, int memkind);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

@@ -514,6 +514,53 @@ class Context:
         lim = np.ascontiguousarray(limits, dtype=np.float32)
         return self._ensemble("mifc_probability", fields, fdefined_in, [int(compute)], [lim.ctypes.data, int(lim.size)], fdefined, undef, out)
 
+    def ensembleQuantiles(self, fields, percentiles, fdefined_in=None, method="lower", undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_ensembleQuantiles): per-cell percentiles across ensemble members.
+        fields: a sequence of members, each (ny, nx) or (nlev, ny, nx), or one stacked array / tensor whose axis 0 is the
+        members (numpy: host memory, CUDA tensors: device).  percentiles: one value or a sequence in [0, 100].
+        fdefined_in: member flags, (nmem,) or (nmem, nlev); None: SOME_DEFINED.  method: "lower" (the reference's
+        neighbourFunctions rule) or "linear" (numpy's default).  out: (nq,) + the member shape, may be the members
+        themselves.  Returns (out, fdefined): an int for 2-D members, an int32 array of nlev flags otherwise.  A refused
+        call raises RuntimeError with the reason."""
+        code = {"lower": 0, "linear": 1}.get(method, -1) if isinstance(method, str) else int(method)
+        members = [fields[j] for j in range(fields.shape[0])] if isinstance(fields, np.ndarray) or _is_torch(fields) else list(fields)
+        pct = np.ascontiguousarray(np.asarray(percentiles, dtype=np.float32).ravel())
+        nq = int(pct.size)
+        fa = [_Arg(m) for m in members]
+        if fa:
+            shape = tuple(fa[0].shape)
+        elif out is not None:
+            shape = tuple(_Arg(out, output=True).shape)[1:]
+        else:
+            raise ValueError("no member fields and no output to take the shape from")
+        if len(shape) not in (2, 3):
+            raise ValueError("members must be (ny, nx) or (nlev, ny, nx) fields")
+        if not _same_shape(fa, shape):
+            raise ValueError("every member must have the shape %s" % (shape,))
+        nlev = shape[0] if len(shape) == 3 else 1
+        ny, nx = shape[-2], shape[-1]
+        if out is None:
+            out = _empty_like(members[0], (nq,) + shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != (nq,) + shape:
+            raise ValueError("out must have shape %s" % (((nq,) + shape),))
+        mk = _memkind(fa + [oa], self.device)
+        self._bind_stream(mk)
+        level_bytes = nlev * ny * nx * 4
+        table = (ctypes.c_void_p * max(len(fa), 1))(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * max(nq, 1))(*[oa.addr + q * level_bytes for q in range(nq)])
+        flags = None
+        if fdefined_in is not None:
+            f = np.asarray(fdefined_in, dtype=np.int32)
+            if f.ndim == 1:
+                f = np.repeat(f[:, None], nlev, axis=1)
+            flags = np.ascontiguousarray(f.reshape(len(fa), nlev), dtype=np.int32)
+        fd = np.zeros(nlev, np.int32)
+        if not self._call("mifc_ensembleQuantiles", [code, nx, ny, nlev, ctypes.addressof(table), flags, len(fa), pct, nq, ctypes.addressof(outs), fd,
+                                                      float(undef), mk]):
+            raise RuntimeError("mifc_ensembleQuantiles: " + self.last_error())
+        return (out if _is_torch(out) else oa.keep), (int(fd[0]) if len(shape) == 2 else fd)
+
     # ------------------------------------------------------ neighbourhood statistics
     # out=None allocates an output pre-filled with `undef`: the reference leaves some cells unwritten (neighbourFunctions:
     # interior cells that no step x step block covers; neighbourProbFunctions with range 0 and a compute other than 5 / 6:

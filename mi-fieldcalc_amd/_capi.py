@@ -122,6 +122,8 @@ SIGNATURES = {
     "mifc_stddevValue": ("i", ["ctx", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_extremeValue": ("i", ["ctx", "i", "i", "i", "p", "i", "p", "pi", "f", "i"]),
     "mifc_probability": ("i", ["ctx", "i", "i", "i", "p", "p", "i", "p", "i", "p", "pi", "f", "i"]),
+    # EXTENSION: percentiles across members (fields, fres: host tables of pointers; percentiles: host float array)
+    "mifc_ensembleQuantiles": ("i", ["ctx", "i", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "f", "i"]),
     # neighbourhood statistics (constants: host float array)
     "mifc_neighbourProbFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_neighbourFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),

@@ -196,6 +196,52 @@ struct EnsembleParams
 };
 hipError_t launch_ensemble(const EnsembleParams& prm, hipStream_t stream);
 
+// ------------------------------------ percentiles across ensemble members (mifc_quantile.hip), EXTENSION
+// One launch covers `nlev` levels of `n` cells each; member j's level l is mem(j) + l * stride, output q's likewise.
+// Members, percentiles, outputs and the per-level ALL_DEFINED member bits travel in the kernel arguments when they fit
+// (nmem <= 64, nq <= QUANTILE_KARG_Q, every level of the call < QUANTILE_KARG_LEVELS), in the device table otherwise.
+// The host has validated every percentile (0 <= p <= 100) and keeps the outputs apart from the members.
+const int QUANTILE_KARG_MEM = 64, QUANTILE_KARG_Q = 16, QUANTILE_KARG_LEVELS = 64;
+struct QuantileTable // device memory, used when inline_args == 0
+{
+  const float* const* mem; // [nmem]
+  float* const* out;       // [nq]
+  const float* p;          // [nq]
+  const u64* all_bits;     // [level][words]: bit j % 64 of word j / 64 set = member j's flag is ALL_DEFINED at that level
+};
+struct QuantileParams
+{
+  int nlev;    // levels of this launch
+  int lev0;    // the call's level of the launch's level 0 (member bits, counters)
+  int n;       // cells per level
+  long stride; // floats between consecutive levels of every member and output of the launch
+  int nmem, nq;
+  int method;  // MIFC_QUANTILE_LOWER / MIFC_QUANTILE_LINEAR
+  int words;   // (nmem + 63) / 64
+  float undef;
+  u64* n_undefined;       // [call levels]: cells without a defined member, at lev0 + l (zeroed by the caller)
+  unsigned int* partials; // per-workgroup counts of big launches (see EwiseParams), or null
+  int partials_cap;
+  int inline_args;
+  QuantileTable tab;
+  const float* mem_inline[QUANTILE_KARG_MEM];
+  float* out_inline[QUANTILE_KARG_Q];
+  float p_inline[QUANTILE_KARG_Q];
+  u64 all_inline[QUANTILE_KARG_LEVELS]; // nmem <= 64: one word per level
+};
+// the sorting-network capacity that holds nmem members (8, 16, 32, 64), or 0: the bisection path (nmem > 64)
+inline int quantile_tier(int nmem)
+{
+  return nmem <= 8 ? 8 : nmem <= 16 ? 16 : nmem <= 32 ? 32 : nmem <= 64 ? 64 : 0;
+}
+// workgroups per level of a launch over n cells (the host sizes the partial-count buffer with it)
+inline int quantile_blocks(int n)
+{
+  const long want = ((long)n + 255) / 256;
+  return (int)(want < 1 ? 1 : (want > 65535 ? 65535 : want));
+}
+hipError_t launch_quantiles(const QuantileParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Percentiles across ensemble members: mifc_ensembleQuantiles on 51 device-resident members of 1440x720 (nlev 1 and
+10, nq 1 and 5, both methods) -- median synchronous call time (host clock around the call and a device synchronise)
+and summed kernel time (HIP events around the launches, measurement build), algorithmic bytes ((nmem + nq) x 4 B per
+cell: every member read once, every output written once), fraction of 8 TB/s -- next to meanValue on the same members
+(one call per level) as the yardstick, in the same process on the same buffers.
+
+    python tools/bench_ensemble_quantiles.py   -> one JSON line per (nlev, nq, method), then one per yardstick
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*: measurement build
+
+import torch  # noqa: E402
+
+import mi_fieldcalc_amd as fc  # noqa: E402
+
+NX, NY, NMEM = 1440, 720, 51
+PEAK = 8000.0  # GB/s
+ROUNDS = 9
+PS = {1: [50.0], 5: [10.0, 25.0, 50.0, 75.0, 90.0]}
+
+
+def timed(ctx, call):
+    assert call() is not None, ctx.last_error()  # warm-up
+    torch.cuda.synchronize()
+    ts, ks = [], []
+    for _ in range(ROUNDS):
+        ctx.timing_begin()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+        ks.append(ctx.timing_end_ms())
+    return float(np.median(ts)), float(np.median(ks))
+
+
+def main():
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(2024)
+    with fc.Context(0) as ctx:
+        for nlev in (1, 10):
+            members = torch.randn((NMEM, nlev, NY, NX), generator=gen, device=dev, dtype=torch.float32) * 3 + 273
+            cells = nlev * NX * NY
+            for nq in (1, 5):
+                out = torch.empty((nq, nlev, NY, NX), device=dev, dtype=torch.float32)
+                for method in ("lower", "linear"):
+                    ms, kms = timed(ctx, lambda: ctx.ensembleQuantiles(members, PS[nq], method=method, out=out))  # noqa: B023
+                    alg = (NMEM + nq) * 4 * cells
+                    print(json.dumps({"call": "ensembleQuantiles", "method": method, "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev, "nq": nq,
+                                      "ms": round(ms, 4), "kernel_ms": round(kms, 4), "algorithmic_bytes": alg,
+                                      "frac_of_8TBps": round(alg / ms / 1e6 / PEAK, 4),
+                                      "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}), flush=True)
+            # yardstick: meanValue over the same members, one call per level (it takes 2-D fields)
+            mean_out = torch.empty((NY, NX), device=dev, dtype=torch.float32)
+            per_level = [[members[j, l] for j in range(NMEM)] for l in range(nlev)]
+            flags = [fc.SOME_DEFINED] * NMEM
+
+            def means():
+                for lv in per_level:
+                    r = ctx.meanValue(lv, flags, out=mean_out)
+                return r
+
+            ms, kms = timed(ctx, means)
+            alg = (NMEM + 1) * 4 * cells
+            print(json.dumps({"call": "meanValue (yardstick, one call per level)", "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev, "ms": round(ms, 4),
+                              "kernel_ms": round(kms, 4), "algorithmic_bytes": alg, "frac_of_8TBps": round(alg / ms / 1e6 / PEAK, 4),
+                              "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}), flush=True)
+            del members
+
+
+if __name__ == "__main__":
+    main()
