@@ -18,77 +18,6 @@
 
 namespace mifc_host {
 
-
-bool fail(mifc_ctx* c, const char* what, hipError_t e)
-{
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  if (c)
-    c->err = buf;
-  return false;
-}
-
-
-bool ensure_slot(mifc_ctx* c, int s, size_t bytes)
-{
-  if (c->slot_bytes[s] >= bytes)
-    return true;
-  if (c->slot[s]) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-      return fail(c, "hipStreamSynchronize", e);
-    (void)hipFree(c->slot[s]);
-    c->slot[s] = nullptr;
-    c->slot_bytes[s] = 0;
-  }
-  const size_t want = (bytes + 255) & ~size_t(255);
-  hipError_t e = hipMalloc(&c->slot[s], want);
-  if (e != hipSuccess)
-    return fail(c, "hipMalloc(scratch)", e);
-  c->slot_bytes[s] = want;
-  return true;
-}
-
-bool ensure_levels(mifc_ctx* c, size_t nlev)
-{
-  if (c->cap_lev >= nlev)
-    return true;
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess)
-    return fail(c, "hipStreamSynchronize", e);
-  if (c->d_flags)
-    (void)hipFree(c->d_flags);
-  if (c->d_counts)
-    (void)hipFree(c->d_counts);
-  if (c->d_ab)
-    (void)hipFree(c->d_ab);
-  if (c->d_levels)
-    (void)hipFree(c->d_levels);
-  if (c->h_pinned)
-    (void)hipHostFree(c->h_pinned);
-  c->d_levels = nullptr;
-  c->d_flags = nullptr;
-  c->d_counts = nullptr;
-  c->d_ab = nullptr;
-  c->h_pinned = nullptr;
-  c->cap_lev = 0;
-  size_t cap = 256;
-  while (cap < nlev)
-    cap *= 2;
-  if ((e = hipMalloc((void**)&c->d_flags, 2 * cap)) != hipSuccess)
-    return fail(c, "hipMalloc(flags)", e);
-  if ((e = hipMalloc((void**)&c->d_counts, 5 * cap * sizeof(u64))) != hipSuccess)
-    return fail(c, "hipMalloc(counts)", e);
-  if ((e = hipMalloc((void**)&c->d_ab, 2 * cap * sizeof(float))) != hipSuccess)
-    return fail(c, "hipMalloc(ab)", e);
-  if ((e = hipMalloc((void**)&c->d_levels, cap * sizeof(int))) != hipSuccess)
-    return fail(c, "hipMalloc(levels)", e);
-  if ((e = hipHostMalloc(&c->h_pinned, 5 * cap * sizeof(u64) + 2 * cap + 2 * cap * sizeof(float), hipHostMallocDefault)) != hipSuccess)
-    return fail(c, "hipHostMalloc", e);
-  c->cap_lev = cap;
-  return true;
-}
-
 // One tested level of a big field through the one-shot stencil kernels: room for their workgroups' counts (StencilParams::partials).
 // Not while a capture is recorded (the buffer is the context's ONE, calls recorded side by side would share it; and growing
 // it frees memory): those launches keep one atomic per workgroup.
@@ -109,124 +38,6 @@ void stencil_partials(mifc_ctx* c, mifc::StencilParams& P)
   P.partials_cap = P.partials ? cap : 0;
 }
 
-unsigned int* partials_for(mifc_ctx* c, size_t n_cells, int* cap)
-{
-  *cap = 0;
-  const size_t blocks = (n_cells / 4 + 255) / 256; // one float4 per lane, 256 lanes
-  if (blocks < 2048)
-    return nullptr;
-  if (blocks > c->partials_cap) {
-    if (c->d_partials)
-      (void)hipFree(c->d_partials);
-    c->d_partials = nullptr;
-    c->partials_cap = 0;
-    if (hipMalloc((void**)&c->d_partials, blocks * sizeof(unsigned int)) != hipSuccess)
-      return nullptr; // the launch then counts with one atomic per workgroup
-    c->partials_cap = blocks;
-  }
-  *cap = (int)c->partials_cap;
-  return c->d_partials;
-}
-
-bool pinned_acquire(mifc_ctx* c)
-{
-  if (c->pinned_read_pending) {
-    hipError_t e = hipEventSynchronize(c->pinned_read);
-    if (e != hipSuccess)
-      return fail(c, "hipEventSynchronize", e);
-    c->pinned_read_pending = false;
-  }
-  return true;
-}
-
-bool pinned_release(mifc_ctx* c)
-{
-  hipError_t e = hipEventRecord(c->pinned_read, c->stream);
-  if (e != hipSuccess)
-    return fail(c, "hipEventRecord", e);
-  c->pinned_read_pending = true;
-  return true;
-}
-
-bool scratch_release(mifc_ctx* c)
-{
-  if (c->capturing && c->n_lanes > 1) {
-    // the context's per-level scratch (flags, hybrid coefficients) is ONE set: calls recorded side by side would overwrite it
-    // under each other's kernels
-    c->err = "a call that needs the context's per-level scratch was recorded into a capture with several lanes: record level batches of at most 8 "
-             "levels (their flags and coefficients travel in the kernel arguments), or use one lane";
-    return false;
-  }
-  hipError_t e = hipEventRecord(c->scratch_read, c->stream);
-  if (e != hipSuccess)
-    return fail(c, "hipEventRecord", e);
-  c->scratch_read_pending = true;
-  return true;
-}
-
-u64* pinned_counts(mifc_ctx* c)
-{
-  return reinterpret_cast<u64*>(c->h_pinned);
-}
-unsigned char* pinned_flags(mifc_ctx* c)
-{
-  return reinterpret_cast<unsigned char*>(c->h_pinned) + 5 * c->cap_lev * sizeof(u64);
-}
-float* pinned_ab(mifc_ctx* c)
-{
-  return reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(c->h_pinned) + 5 * c->cap_lev * sizeof(u64) + 2 * c->cap_lev);
-}
-
-// Brings a field to the device if the caller handed a host pointer.
-const float* stage_in(mifc_ctx* c, int s, const float* p, size_t n, int memkind, bool* ok)
-{
-  if (!p || memkind == MIFC_MEM_DEVICE)
-    return p;
-  for (const mifc_ctx::HeldField& h : c->held)
-    if (h.host == p && h.n >= n)
-      return h.dev; // declared constant by the caller: already resident
-  if (!ensure_slot(c, s, n * sizeof(float))) {
-    *ok = false;
-    return nullptr;
-  }
-  hipError_t e = hipMemcpyAsync(c->slot[s], p, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) {
-    fail(c, "hipMemcpyAsync(H2D)", e);
-    *ok = false;
-    return nullptr;
-  }
-  return static_cast<const float*>(c->slot[s]);
-}
-
-float* stage_out(mifc_ctx* c, int s, float* p, size_t n, int memkind, bool* ok, bool preload)
-{
-  if (!p || memkind == MIFC_MEM_DEVICE)
-    return p;
-  if (!ensure_slot(c, s, n * sizeof(float))) {
-    *ok = false;
-    return nullptr;
-  }
-  if (preload) { // operator may leave cells unwritten: start from the caller's content
-    hipError_t e = hipMemcpyAsync(c->slot[s], p, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-      fail(c, "hipMemcpyAsync(H2D)", e);
-      *ok = false;
-      return nullptr;
-    }
-  }
-  return static_cast<float*>(c->slot[s]);
-}
-
-bool fetch_out(mifc_ctx* c, int s, float* p, size_t n, int memkind)
-{
-  if (!p || memkind == MIFC_MEM_DEVICE)
-    return true;
-  hipError_t e = hipMemcpyAsync(p, c->slot[s], n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e != hipSuccess)
-    return fail(c, "hipMemcpyAsync(D2H)", e);
-  return true;
-}
-
 inline bool unit_is(const char* unit, const char* what)
 {
   return unit && std::strcmp(unit, what) == 0;
@@ -243,12 +54,12 @@ int run_ewise(mifc_ctx* c, mifc::EwiseParams P, const float* in0, const float* i
               bool may_keep)
 {
   const size_t n = (size_t)P.n;
-  bool ok = true;
-  P.in0 = stage_in(c, 0, in0, n, memkind, &ok);
-  P.in1 = stage_in(c, 1, in1, n, memkind, &ok);
-  P.in2 = stage_in(c, 2, in2, n, memkind, &ok);
-  P.out = stage_out(c, 3, out, n, memkind, &ok, may_keep);
-  if (!ok || !ensure_levels(c, 1))
+  Staging st(c, memkind);
+  P.in0 = st.in(in0, n);
+  P.in1 = st.in(in1, n);
+  P.in2 = st.in(in2, n);
+  P.out = st.out(out, n, may_keep);
+  if (!st.ok() || !ensure_levels(c, 1))
     return 0;
   // With an ALL_DEFINED input nothing is tested, and the operators without a saturation table cannot
   // reject a cell on their own: the count is known to be zero, no counter round trip (5 us of a 19 us call)
@@ -266,9 +77,8 @@ int run_ewise(mifc_ctx* c, mifc::EwiseParams P, const float* in0, const float* i
   MIFC_LAUNCH(c, mifc::launch_ewise(P, c->stream));
   if (counted)
     MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  if (!fetch_out(c, 3, out, n, memkind))
+  if (!st.finish())
     return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
   if (counted)
     *fdefined = mifc_classify(pinned_counts(c)[0], (u64)n);
   else if (want_flag)
@@ -323,7 +133,7 @@ int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, 
     return 0;
   const size_t n = (size_t)sc.nx * sc.ny;
   const size_t nb = n * (size_t)sc.nlev;
-  bool ok = true;
+  Staging st(c, memkind);
   mifc::StencilParams P;
   std::memset(&P, 0, sizeof P);
   P.op = sc.op;
@@ -346,20 +156,20 @@ int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, 
     P.out0 = sc.o0;
     P.out1 = sc.o1;
   } else {
-    P.f0 = stage_in(c, 0, sc.f0, nb, memkind, &ok);
-    P.f1 = stage_in(c, 1, sc.f1, nb, memkind, &ok);
-    P.out0 = stage_out(c, 5, sc.o0, nb, memkind, &ok);
-    P.out1 = stage_out(c, 6, sc.o1, nb, memkind, &ok);
-    P.f2 = stage_in(c, 7, sc.f2, nb, memkind, &ok);
+    P.f0 = st.in(sc.f0, nb);
+    P.f1 = st.in(sc.f1, nb);
+    P.out0 = st.out(sc.o0, nb);
+    P.out1 = st.out(sc.o1, nb);
+    P.f2 = st.in(sc.f2, nb);
   }
-  P.xmapr = stage_in(c, 2, sc.xm, n, memkind, &ok);
-  P.ymapr = stage_in(c, 3, sc.ym, n, memkind, &ok);
-  P.fcoriolis = stage_in(c, 4, sc.fc, n, memkind, &ok);
+  P.xmapr = st.in(sc.xm, n);
+  P.ymapr = st.in(sc.ym, n);
+  P.fcoriolis = st.in(sc.fc, n);
   P.scale = sc.scale;
   P.scale2 = sc.scale2;
   P.scale_lev = sc.scale_lev;
   P.scale2_lev = sc.scale2_lev;
-  if (!ok || !ensure_levels(c, (size_t)sc.nlev))
+  if (!st.ok() || !ensure_levels(c, (size_t)sc.nlev))
     return 0;
   if (sc.op == mifc::ST_VORTDIV && !P.out0 && P.out1) {
     // only divergence requested
@@ -428,10 +238,9 @@ int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, 
     MIFC_LAUNCH(c, mifc::launch_stencil(P, c->stream));
     if (!every_all)
       MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, sizeof(u64) * (size_t)sc.nlev, hipMemcpyDeviceToHost, c->stream));
-    if (!fetch_out(c, 5, sc.o0, nb, memkind) || !fetch_out(c, 6, sc.o1, nb, memkind))
-      return 0;
   }
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
+  if (!st.finish()) // (the chunked pipeline has delivered its outputs itself: nothing was staged for them)
+    return 0;
   const u64 denom = stencil_denominator(sc.op, sc.nx, sc.ny);
   for (int l = 0; l < sc.nlev; ++l) {
     if (sc.op == mifc::ST_GWIND_X)
@@ -502,9 +311,7 @@ void mifc_destroy(mifc_ctx* c)
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   (void)mifc_comm_release(c); // a communicator the library created goes with the context
-  for (int s = 0; s < mifc_ctx::NSLOT; ++s)
-    if (c->slot[s])
-      (void)hipFree(c->slot[s]);
+  free_slots(c);
   if (c->d_flags)
     (void)hipFree(c->d_flags);
   if (c->d_counts)
@@ -554,9 +361,7 @@ static int switch_stream(mifc_ctx* c, hipStream_t s)
 
 int mifc_set_stream(mifc_ctx* c, void* hip_stream)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (c->capturing) {
     c->err = "mifc_set_stream: a graph capture is open on this context (mifc_graph_begin)";
     return 0;
@@ -566,9 +371,7 @@ int mifc_set_stream(mifc_ctx* c, void* hip_stream)
 
 int mifc_use_own_stream(mifc_ctx* c)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (c->capturing) {
     c->err = "mifc_use_own_stream: a graph capture is open on this context (mifc_graph_begin)";
     return 0;
@@ -585,9 +388,7 @@ int mifc_not_built(mifc_ctx* c, const char* what)
 
 int mifc_synchronize(mifc_ctx* c)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   MIFC_HIP(c, hipStreamSynchronize(c->stream));
   return 1;
 }
@@ -607,18 +408,14 @@ void* mifc_device_alloc(mifc_ctx* c, size_t bytes)
 
 int mifc_device_free(mifc_ctx* c, void* dptr)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   MIFC_HIP(c, hipFree(dptr));
   return 1;
 }
 
 int mifc_copy_to_device(mifc_ctx* c, void* dst_dev, const void* src_host, size_t bytes)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   MIFC_HIP(c, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c->stream));
   MIFC_HIP(c, hipStreamSynchronize(c->stream));
   return 1;
@@ -626,9 +423,7 @@ int mifc_copy_to_device(mifc_ctx* c, void* dst_dev, const void* src_host, size_t
 
 int mifc_copy_to_host(mifc_ctx* c, void* dst_host, const void* src_dev, size_t bytes)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   MIFC_HIP(c, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
   MIFC_HIP(c, hipStreamSynchronize(c->stream));
   return 1;
@@ -675,9 +470,7 @@ int mifc_hold_field(mifc_ctx* c, const float* host_field, size_t n_floats)
 
 int mifc_release_field(mifc_ctx* c, const float* host_field)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   for (size_t k = 0; k < c->held.size(); ++k) {
     if (c->held[k].host == host_field) {
       MIFC_HIP(c, hipStreamSynchronize(c->stream));
@@ -695,9 +488,7 @@ int mifc_release_field(mifc_ctx* c, const float* host_field)
 // (-1 on error, or when more than 16 launches happened in between).
 int mifc_timing_begin(mifc_ctx* c)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   for (hipEvent_t& e : c->tev)
     if (!e)
       MIFC_HIP(c, hipEventCreate(&e));
@@ -753,9 +544,7 @@ int mifc_classify(unsigned long long n_undefined, unsigned long long n)
 
 int mifc_vectorabs(mifc_ctx* c, int nx, int ny, const float* u, const float* v, float* ff, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (nx * ny <= 0) { // empty loop, checkDefined(0, 0)
     *fdefined = MIFC_ALL_DEFINED;
     return 1;
@@ -767,9 +556,7 @@ int mifc_vectorabs(mifc_ctx* c, int nx, int ny, const float* u, const float* v, 
 int mifc_pleveltemp(mifc_ctx* c, int nx, int ny, const float* tinp, float p, const char* unit, int compute, float* tout, int* fdefined, float undef,
                     int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (p <= 0) // FieldCalculations.cc:330
     return 0;
   if (compute < 3) { // :340-345
@@ -798,9 +585,7 @@ int mifc_pleveltemp(mifc_ctx* c, int nx, int ny, const float* tinp, float p, con
 int mifc_hleveltemp(mifc_ctx* c, int nx, int ny, const float* tinp, const float* ps, float alevel, float blevel, const char* unit, int compute,
                     float* tout, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (compute < 3) { // :1060-1065
     if (unit_is(unit, "celsius"))
       compute = 1;
@@ -824,9 +609,7 @@ int mifc_hleveltemp(mifc_ctx* c, int nx, int ny, const float* tinp, const float*
 int mifc_aleveltemp(mifc_ctx* c, int nx, int ny, const float* tinp, const float* p, const char* unit, int compute, float* tout, int* fdefined,
                     float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (compute <= 0 || compute >= 6) // :1319
     return 0;
   if (compute < 3) {
@@ -859,9 +642,7 @@ static int hum_kind_ah(int compute) // numbering of alevelhum / hlevelhum (:1157
 int mifc_plevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* huminp, float p, const char* unit, int compute, float* humout,
                    int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (p <= 0 || compute <= 0 || compute >= 13) // :419
     return 0;
   if (compute > 8 && unit_is(unit, "celsius")) // :422-425
@@ -875,16 +656,15 @@ int mifc_plevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* hum
   P.p = p;
   if (p == undef && !rh_td) { // :429-432 fillUndef (:76-82): result undef everywhere, NONE_DEFINED
     if (n > 0) {
-      bool ok = true;
-      float* out = stage_out(c, 3, humout, (size_t)n, memkind, &ok);
-      if (!ok)
+      Staging st(c, memkind);
+      float* out = st.out(humout, (size_t)n);
+      if (!st.ok())
         return 0;
       unsigned int bits;
       std::memcpy(&bits, &undef, sizeof bits);
       MIFC_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), (int)bits, (size_t)n, c->stream));
-      if (!fetch_out(c, 3, humout, (size_t)n, memkind))
+      if (!st.finish())
         return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
     }
     *fdefined = MIFC_NONE_DEFINED;
     return 1;
@@ -912,9 +692,7 @@ int mifc_plevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* hum
 int mifc_hlevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* huminp, const float* ps, float alevel, float blevel, const char* unit,
                    int compute, float* humout, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (compute <= 0 || compute >= 13) // :1168
     return 0;
   if (bad_hlevel(alevel, blevel)) // :1170
@@ -942,9 +720,7 @@ int mifc_hlevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* hum
 int mifc_alevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* huminp, const float* p, const char* unit, int compute, float* humout,
                    int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (compute <= 0 || compute >= 13) // :1414
     return 0;
   if (compute > 8 && unit_is(unit, "celsius")) // :1417-1420
@@ -970,9 +746,7 @@ int mifc_alevelhum(mifc_ctx* c, int nx, int ny, const float* t, const float* hum
 int mifc_cvhum(mifc_ctx* c, int nx, int ny, const float* t, const float* huminp, const char* unit, int compute, float* humout, int* fdefined,
                float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   float unit_scale = 100; // :1746-1750
   if (compute == 1 && unit_is(unit, "celsius"))
     compute = 2;
@@ -996,9 +770,7 @@ int mifc_cvhum(mifc_ctx* c, int nx, int ny, const float* t, const float* huminp,
 int mifc_relvort(mifc_ctx* c, int nx, int ny, const float* u, const float* v, const float* xmapr, const float* ymapr, float* rvort, int* fdefined,
                  float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_RELVORT, nx, ny, 1, u, v, xmapr, ymapr, nullptr, rvort, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1006,9 +778,7 @@ int mifc_relvort(mifc_ctx* c, int nx, int ny, const float* u, const float* v, co
 int mifc_absvort(mifc_ctx* c, int nx, int ny, const float* u, const float* v, const float* xmapr, const float* ymapr, const float* fcoriolis,
                  float* avort, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_ABSVORT, nx, ny, 1, u, v, xmapr, ymapr, fcoriolis, avort, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1016,9 +786,7 @@ int mifc_absvort(mifc_ctx* c, int nx, int ny, const float* u, const float* v, co
 int mifc_divergence(mifc_ctx* c, int nx, int ny, const float* u, const float* v, const float* xmapr, const float* ymapr, float* diverg,
                     int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_DIVERGENCE, nx, ny, 1, u, v, xmapr, ymapr, nullptr, diverg, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1026,9 +794,7 @@ int mifc_divergence(mifc_ctx* c, int nx, int ny, const float* u, const float* v,
 int mifc_gradient(mifc_ctx* c, int nx, int ny, const float* field, const float* xmapr, const float* ymapr, int compute, float* fgrad, int* fdefined,
                   float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (compute < 1 || compute > 4) // :2064 (size check comes first in the reference, both return false)
     return 0;
   const int op = mifc::ST_GRAD_X + (compute - 1);
@@ -1039,9 +805,7 @@ int mifc_gradient(mifc_ctx* c, int nx, int ny, const float* field, const float* 
 int mifc_plevelgwind_xcomp(mifc_ctx* c, int nx, int ny, const float* z, const float* xmapr, const float* ymapr, const float* fcoriolis, float* ug,
                            int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   (void)xmapr; // unused by the reference as well (:638)
   const StencilCall sc = {mifc::ST_GWIND_X, nx, ny, 1, z, nullptr, nullptr, ymapr, fcoriolis, ug, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
@@ -1050,9 +814,7 @@ int mifc_plevelgwind_xcomp(mifc_ctx* c, int nx, int ny, const float* z, const fl
 int mifc_plevelgwind_ycomp(mifc_ctx* c, int nx, int ny, const float* z, const float* xmapr, const float* ymapr, const float* fcoriolis, float* vg,
                            int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   (void)ymapr;
   // the reference lacks the nx<3||ny<3 guard here and would read out of bounds;
   // this implementation returns false instead
@@ -1063,9 +825,7 @@ int mifc_plevelgwind_ycomp(mifc_ctx* c, int nx, int ny, const float* z, const fl
 int mifc_plevelgvort(mifc_ctx* c, int nx, int ny, const float* z, const float* xmapr, const float* ymapr, const float* fcoriolis, float* gvort,
                      int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_GVORT, nx, ny, 1, z, nullptr, xmapr, ymapr, fcoriolis, gvort, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1073,9 +833,7 @@ int mifc_plevelgvort(mifc_ctx* c, int nx, int ny, const float* z, const float* x
 int mifc_ilevelgwind(mifc_ctx* c, int nx, int ny, const float* mpot, const float* xmapr, const float* ymapr, const float* fcoriolis, float* ug,
                      float* vg, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_IGWIND, nx, ny, 1, mpot, nullptr, xmapr, ymapr, fcoriolis, ug, vg};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1085,9 +843,7 @@ int mifc_ilevelgwind(mifc_ctx* c, int nx, int ny, const float* mpot, const float
 int mifc_advection(mifc_ctx* c, int nx, int ny, const float* f, const float* u, const float* v, const float* xmapr, const float* ymapr, float hours,
                    float* advec, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   StencilCall sc = {mifc::ST_ADVECTION, nx, ny, 1, f, u, xmapr, ymapr, nullptr, advec, nullptr};
   sc.f2 = v;
   sc.scale = (float)(-3600. * (double)hours); // FieldCalculations.cc:1963
@@ -1097,9 +853,7 @@ int mifc_advection(mifc_ctx* c, int nx, int ny, const float* f, const float* u, 
 int mifc_jacobian(mifc_ctx* c, int nx, int ny, const float* field1, const float* field2, const float* xmapr, const float* ymapr, float* fjacobian,
                   int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const StencilCall sc = {mifc::ST_JACOBIAN, nx, ny, 1, field1, field2, xmapr, ymapr, nullptr, fjacobian, nullptr};
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
@@ -1107,9 +861,7 @@ int mifc_jacobian(mifc_ctx* c, int nx, int ny, const float* field1, const float*
 static int momentum_coordinate(mifc_ctx* c, int op, int nx, int ny, const float* wind, const float* mapr, const float* fcoriolis, float fcoriolisMin,
                                float* out, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (nx < 3 || ny < 3) // :2363, :2397
     return 0;
   mifc::EwiseParams P = ewise_base(op, nx, ny, fdefined, undef);
@@ -1169,9 +921,10 @@ static int tfp_two_passes(mifc_ctx* c, int nx, int ny, const float* d_tx, const 
                           float undef, int nlev = 1)
 {
   const size_t n = (size_t)nx * ny;
-  if (!ensure_slot(c, 8, n * (size_t)nlev * sizeof(float)))
+  Staging st(c, MIFC_MEM_DEVICE);
+  float* d_absdelt = static_cast<float*>(st.scratch(n * (size_t)nlev * sizeof(float)));
+  if (!st.ok())
     return 0;
-  float* d_absdelt = static_cast<float*>(c->slot[8]);
   const StencilCall pass1 = {mifc::ST_GRAD_ABS, nx, ny, nlev, d_tx, nullptr, d_xm, d_ym, nullptr, d_absdelt, nullptr};
   if (!run_stencil(c, pass1, fdefined, undef, MIFC_MEM_DEVICE))
     return 0;
@@ -1186,19 +939,17 @@ static int tfp_two_passes(mifc_ctx* c, int nx, int ny, const float* d_tx, const 
 int mifc_thermalFrontParameter(mifc_ctx* c, int nx, int ny, const float* tx, const float* xmapr, const float* ymapr, float* tfp, int* fdefined,
                                float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (nx < 3 || ny < 3) // gradient() :2004
     return 0;
   const size_t n = (size_t)nx * ny;
-  bool ok = true;
+  Staging st(c, memkind);
   // bring the inputs to the device once; both passes then run on device pointers
-  const float* d_tx = stage_in(c, 0, tx, n, memkind, &ok);
-  const float* d_xm = stage_in(c, 2, xmapr, n, memkind, &ok);
-  const float* d_ym = stage_in(c, 3, ymapr, n, memkind, &ok);
-  float* d_out = stage_out(c, 5, tfp, n, memkind, &ok);
-  if (!ok)
+  const float* d_tx = st.in(tx, n);
+  const float* d_xm = st.in(xmapr, n);
+  const float* d_ym = st.in(ymapr, n);
+  float* d_out = st.out(tfp, n);
+  if (!st.ok())
     return 0;
   if (fused2_enabled()) {
     mifc::Fused2Params F;
@@ -1214,19 +965,12 @@ int mifc_thermalFrontParameter(mifc_ctx* c, int nx, int ny, const float* tx, con
     const int r = run_fused2(c, F, fdefined);
     if (r == 0)
       return 0;
-    if (r == 1) {
-      if (!fetch_out(c, 5, tfp, n, memkind))
-        return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
-      return 1;
-    }
+    if (r == 1)
+      return st.finish();
   }
   if (!tfp_two_passes(c, nx, ny, d_tx, d_xm, d_ym, d_out, fdefined, undef))
     return 0;
-  if (!fetch_out(c, 5, tfp, n, memkind))
-    return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return st.finish();
 }
 
 // plevelqvector, FieldCalculations.cc:505-595: geostrophic wind x and y into
@@ -1236,9 +980,7 @@ int mifc_thermalFrontParameter(mifc_ctx* c, int nx, int ny, const float* tx, con
 int mifc_plevelqvector(mifc_ctx* c, int nx, int ny, const float* z, const float* t, const float* xmapr, const float* ymapr, const float* fcoriolis,
                        float p, int compute, float* qcomp, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (p <= 0.0 || nx < 3 || ny < 3) // :526-530
     return 0;
   float tscale;
@@ -1251,14 +993,14 @@ int mifc_plevelqvector(mifc_ctx* c, int nx, int ny, const float* z, const float*
     return 0;
   }
   const size_t n = (size_t)nx * ny;
-  bool ok = true;
-  const float* d_z = stage_in(c, 0, z, n, memkind, &ok);
-  const float* d_t = stage_in(c, 1, t, n, memkind, &ok);
-  const float* d_xm = stage_in(c, 2, xmapr, n, memkind, &ok);
-  const float* d_ym = stage_in(c, 3, ymapr, n, memkind, &ok);
-  const float* d_fc = stage_in(c, 4, fcoriolis, n, memkind, &ok);
-  float* d_out = stage_out(c, 5, qcomp, n, memkind, &ok);
-  if (!ok)
+  Staging st(c, memkind);
+  const float* d_z = st.in(z, n);
+  const float* d_t = st.in(t, n);
+  const float* d_xm = st.in(xmapr, n);
+  const float* d_ym = st.in(ymapr, n);
+  const float* d_fc = st.in(fcoriolis, n);
+  float* d_out = st.out(qcomp, n);
+  if (!st.ok())
     return 0;
   const float cscale = (float)((double)(-287.f) / ((double)p * 100.)); // :564
   if (fused2_enabled()) {
@@ -1279,17 +1021,13 @@ int mifc_plevelqvector(mifc_ctx* c, int nx, int ny, const float* z, const float*
     const int r = run_fused2(c, F, fdefined);
     if (r == 0)
       return 0;
-    if (r == 1) {
-      if (!fetch_out(c, 5, qcomp, n, memkind))
-        return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
-      return 1;
-    }
+    if (r == 1)
+      return st.finish();
   }
-  if (!ensure_slot(c, 8, n * sizeof(float)) || !ensure_slot(c, 9, n * sizeof(float)))
+  float* d_ug = static_cast<float*>(st.scratch(n * sizeof(float)));
+  float* d_vg = static_cast<float*>(st.scratch(n * sizeof(float)));
+  if (!st.ok())
     return 0;
-  float* d_ug = static_cast<float*>(c->slot[8]);
-  float* d_vg = static_cast<float*>(c->slot[9]);
   const StencilCall pass1 = {mifc::ST_GWIND_X, nx, ny, 1, d_z, nullptr, d_xm, d_ym, d_fc, d_ug, nullptr};
   if (!run_stencil(c, pass1, fdefined, undef, MIFC_MEM_DEVICE))
     return 0;
@@ -1302,10 +1040,7 @@ int mifc_plevelqvector(mifc_ctx* c, int nx, int ny, const float* z, const float*
   pass3.scale2 = cscale;
   if (!run_stencil(c, pass3, fdefined, undef, MIFC_MEM_DEVICE))
     return 0;
-  if (!fetch_out(c, 5, qcomp, n, memkind))
-    return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return st.finish();
 }
 
 // ----------------------------------------------------------------- batched
@@ -1323,9 +1058,7 @@ int mifc_vortdiv_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* u, c
 int mifc_stencil_levels(mifc_ctx* c, int op, int nx, int ny, int nlev, const float* f0, const float* f1, const float* xmapr, const float* ymapr,
                         const float* fcoriolis, float* out0, float* out1, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (!((op >= mifc::ST_RELVORT && op <= mifc::ST_IGWIND) || op == mifc::ST_JACOBIAN) || !f0 || !out0)
     return 0;
   const bool wind = (op <= mifc::ST_VORTDIV) || op == mifc::ST_JACOBIAN; // two input fields per level
@@ -1354,10 +1087,11 @@ static int f1_levels_fallback(mifc_ctx* c, int op, int nx, int ny, int nlev, con
     // the three passes (:555-590), each ONE launch over all levels; the last one takes its two scalars per level from
     // device tables (they depend on the level's pressure)
     const size_t nb = n * (size_t)nlev;
-    if (!ensure_slot(c, 8, nb * sizeof(float)) || !ensure_slot(c, 9, nb * sizeof(float)))
+    Staging st(c, MIFC_MEM_DEVICE);
+    float* d_ug = static_cast<float*>(st.scratch(nb * sizeof(float)));
+    float* d_vg = static_cast<float*>(st.scratch(nb * sizeof(float)));
+    if (!st.ok())
       return 0;
-    float* d_ug = static_cast<float*>(c->slot[8]);
-    float* d_vg = static_cast<float*>(c->slot[9]);
     StencilCall pass1 = {mifc::ST_GWIND_X, nx, ny, nlev, f0, nullptr, xm, ym, fc, d_ug, nullptr};
     if (!run_stencil(c, pass1, fdefined, undef, MIFC_MEM_DEVICE))
       return 0;
@@ -1392,9 +1126,7 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
                            const float* ymapr, const float* fcoriolis, const float* level_scalars, float scalar, int compute, float* out0,
                            float* out1, int* fdefined, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (op != MIFC_OP_ADVECTION && op != MIFC_OP_TFP && op != MIFC_OP_QVECTOR && op != MIFC_OP_SHAPIRO2)
     return mifc_stencil_levels(c, op, nx, ny, nlev, f0, f1, xmapr, ymapr, fcoriolis, out0, out1, fdefined, undef, memkind);
   if (nx < 3 || ny < 3 || nlev < 1 || !f0 || !out0 || !fdefined)
@@ -1427,14 +1159,14 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
       cscale[l] = (float)((double)(-287.f) / ((double)p * 100.)); // :564
     }
   }
-  bool ok = true;
-  const float* d0 = stage_in(c, 0, f0, nb, memkind, &ok);
-  const float* d1 = (op == MIFC_OP_QVECTOR) ? stage_in(c, 1, f1, nb, memkind, &ok) : nullptr;
-  const float* dxm = (op != MIFC_OP_SHAPIRO2) ? stage_in(c, 2, xmapr, n, memkind, &ok) : nullptr;
-  const float* dym = (op != MIFC_OP_SHAPIRO2) ? stage_in(c, 3, ymapr, n, memkind, &ok) : nullptr;
-  const float* dfc = (op == MIFC_OP_QVECTOR) ? stage_in(c, 4, fcoriolis, n, memkind, &ok) : nullptr;
-  float* dout = stage_out(c, 5, out0, nb, memkind, &ok);
-  if (!ok || !ensure_levels(c, (size_t)nlev))
+  Staging st(c, memkind);
+  const float* d0 = st.in(f0, nb);
+  const float* d1 = (op == MIFC_OP_QVECTOR) ? st.in(f1, nb) : nullptr;
+  const float* dxm = (op != MIFC_OP_SHAPIRO2) ? st.in(xmapr, n) : nullptr;
+  const float* dym = (op != MIFC_OP_SHAPIRO2) ? st.in(ymapr, n) : nullptr;
+  const float* dfc = (op == MIFC_OP_QVECTOR) ? st.in(fcoriolis, n) : nullptr;
+  float* dout = st.out(out0, nb);
+  if (!st.ok() || !ensure_levels(c, (size_t)nlev))
     return 0;
   if (op != MIFC_OP_SHAPIRO2 && (!dxm || !dym))
     return 0;
@@ -1452,9 +1184,9 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
   if (op == MIFC_OP_SHAPIRO2) {
     float* dst = dout;
     if (dout == d0) { // in place (allowed by the reference, :2088): through a scratch batch
-      if (!ensure_slot(c, 8, nb * sizeof(float)))
+      dst = static_cast<float*>(st.scratch(nb * sizeof(float)));
+      if (!st.ok())
         return 0;
-      dst = static_cast<float*>(c->slot[8]);
     }
     fused = fused && mifc::env().shapiro_fused && mifc::shapiro2_fused_supported(nx, ny, d0, dst) && (n % 4 == 0 || mifc::env().shapiro_regs);
     if (fused) {
@@ -1465,9 +1197,8 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
         MIFC_LAUNCH(c, mifc::launch_shapiro2_fused_levels(nx, ny, 0, undef, d0, dst, nlev - n_all, (long)n, c->d_levels + n_all, c->stream));
       if (dst != dout)
         MIFC_HIP(c, hipMemcpyAsync(dout, dst, nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      if (!fetch_out(c, 5, out0, nb, memkind))
+      if (!st.finish())
         return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
       for (int l = 0; l < nlev; ++l)
         fdefined[l] = MIFC_ALL_DEFINED; // :2171
       return 1;
@@ -1475,10 +1206,10 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
     // widths the one-launch kernel does not take: the sweep-by-sweep path over the levels of each flag group (five launches
     // per group whatever the number of levels), in place on the output batch like the reference (:2099-2104)
     if (nlev > 1 && nlev <= 65535 && n <= 0x7fffffffu) {
-      if (!ensure_slot(c, 9, nb * sizeof(float)))
-        return 0;
       const bool any_tested = n_all < nlev;
-      if (any_tested && !ensure_slot(c, 7, 2 * nb))
+      float* sweep = static_cast<float*>(st.scratch(nb * sizeof(float)));
+      unsigned char* masks = any_tested ? static_cast<unsigned char*>(st.scratch(2 * nb)) : nullptr;
+      if (!st.ok())
         return 0;
       if (dst != d0)
         MIFC_HIP(c, hipMemcpyAsync(dst, d0, nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -1488,9 +1219,9 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
       SP.ny = ny;
       SP.undef = undef;
       SP.f1 = dst;
-      SP.f2 = static_cast<float*>(c->slot[9]);
-      SP.mask_x = any_tested ? static_cast<unsigned char*>(c->slot[7]) : nullptr;
-      SP.mask_y = any_tested ? static_cast<unsigned char*>(c->slot[7]) + nb : nullptr;
+      SP.f2 = sweep;
+      SP.mask_x = masks;
+      SP.mask_y = any_tested ? masks + nb : nullptr;
       if (n_all > 0) {
         SP.all_defined = 1;
         MIFC_LAUNCH(c, mifc::launch_shapiro2_levels(SP, n_all, c->d_levels, c->stream));
@@ -1501,9 +1232,8 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
       }
       if (dst != dout)
         MIFC_HIP(c, hipMemcpyAsync(dout, dst, nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      if (!fetch_out(c, 5, out0, nb, memkind))
+      if (!st.finish())
         return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
       for (int l = 0; l < nlev; ++l)
         fdefined[l] = MIFC_ALL_DEFINED; // :2171
       return 1;
@@ -1559,20 +1289,14 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
       for (int l : redo) // rare: those levels again, pass by pass
         if (!tfp_two_passes(c, nx, ny, d0 + (size_t)l * n, dxm, dym, dout + (size_t)l * n, fdefined + l, undef))
           return 0;
-      if (!fetch_out(c, 5, out0, nb, memkind))
-        return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
-      return 1;
+      return st.finish();
     }
   }
   // level by level on the staged (device) batch
   if (!f1_levels_fallback(c, op, nx, ny, nlev, d0, d1, dxm, dym, dfc, level_scalars, compute, dout, fdefined, undef,
                           tscale.empty() ? nullptr : tscale.data(), cscale.empty() ? nullptr : cscale.data()))
     return 0;
-  if (!fetch_out(c, 5, out0, nb, memkind))
-    return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return st.finish();
 }
 
 int mifc_vortdiv_levels_enqueue(mifc_ctx* c, int nx, int ny, int nlev, const float* u, const float* v, const float* xmapr, const float* ymapr,
@@ -1802,9 +1526,7 @@ int mifc_stencil_levels_enqueue(mifc_ctx* c, int op, int nx, int ny, int nlev, c
                                 const float* fcoriolis, float* out0, float* out1, const int* fdefined_in, float undef,
                                 unsigned long long* n_undefined_dev)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (!((op >= mifc::ST_RELVORT && op <= mifc::ST_IGWIND) || op == mifc::ST_JACOBIAN) || !f0 || nx < 3 || ny < 3 || nlev < 1 || !xmapr || !ymapr)
     return 0;
   const bool wind = (op <= mifc::ST_VORTDIV) || op == mifc::ST_JACOBIAN; // two input fields per level
@@ -2008,7 +1730,7 @@ int derived_sync(mifc_ctx* c, int nx, int ny, int nlev, const DerivedRequest& rq
   const bool humid = rq0.hum || rq0.hum2;
   const bool wind = rq0.ff || rq0.dd;
   DerivedRequest rq = rq0;
-  bool ok = true;
+  Staging st(c, memkind);
   // (the chunked pipeline carries four outputs; a request with the wind direction on top is staged whole)
   if (memkind == MIFC_MEM_HOST && mifc::hostpipe_chunk_levels(n, nlev) > 0 && host_pipeline_enabled() && !(rq0.dd && rq0.ff && rq0.temp && rq0.hum && rq0.hum2)) {
     // a large batch in host memory: chunks of levels stream through the device, copies
@@ -2017,8 +1739,8 @@ int derived_sync(mifc_ctx* c, int nx, int ny, int nlev, const DerivedRequest& rq
       c->err = "host pipeline: cannot create streams";
       return 0;
     }
-    rq.ps = thermo ? stage_in(c, 4, rq0.ps, n, memkind, &ok) : nullptr;
-    if (!ok || !ensure_levels(c, (size_t)nlev))
+    rq.ps = thermo ? st.in(rq0.ps, n) : nullptr;
+    if (!st.ok() || !ensure_levels(c, (size_t)nlev))
       return 0;
     mifc::DerivedParams base;
     // the host pointers are placeholders that mark which fields take part; the chunk launcher substitutes device buffers
@@ -2080,26 +1802,24 @@ int derived_sync(mifc_ctx* c, int nx, int ny, int nlev, const DerivedRequest& rq
     if (!mifc::hostpipe_run(c->pipe, n, nlev, n_in, h_in, 4, h_out, launch, &c->err))
       return 0;
   } else {
-    rq.u = wind ? stage_in(c, 0, rq0.u, nb, memkind, &ok) : nullptr;
-    rq.v = wind ? stage_in(c, 1, rq0.v, nb, memkind, &ok) : nullptr;
-    rq.t = thermo ? stage_in(c, 2, rq0.t, nb, memkind, &ok) : nullptr;
-    rq.h = humid ? stage_in(c, 3, rq0.h, nb, memkind, &ok) : nullptr;
-    rq.ps = thermo ? stage_in(c, 4, rq0.ps, n, memkind, &ok) : nullptr;
-    rq.ff = stage_out(c, 5, rq0.ff, nb, memkind, &ok);
-    rq.temp = stage_out(c, 6, rq0.temp, nb, memkind, &ok);
-    rq.hum = stage_out(c, 7, rq0.hum, nb, memkind, &ok);
-    rq.hum2 = stage_out(c, 8, rq0.hum2, nb, memkind, &ok);
-    rq.dd = stage_out(c, 9, rq0.dd, nb, memkind, &ok);
-    if (!ok || !ensure_levels(c, (size_t)nlev))
+    rq.u = wind ? st.in(rq0.u, nb) : nullptr;
+    rq.v = wind ? st.in(rq0.v, nb) : nullptr;
+    rq.t = thermo ? st.in(rq0.t, nb) : nullptr;
+    rq.h = humid ? st.in(rq0.h, nb) : nullptr;
+    rq.ps = thermo ? st.in(rq0.ps, n) : nullptr;
+    rq.ff = st.out(rq0.ff, nb);
+    rq.temp = st.out(rq0.temp, nb);
+    rq.hum = st.out(rq0.hum, nb);
+    rq.hum2 = st.out(rq0.hum2, nb);
+    rq.dd = st.out(rq0.dd, nb);
+    if (!st.ok() || !ensure_levels(c, (size_t)nlev))
       return 0;
     if (!derived_common(c, nx, ny, nlev, rq, fdef_wind, fdef_thermo, undef, c->d_counts))
       return 0;
-    if (!fetch_out(c, 5, rq0.ff, nb, memkind) || !fetch_out(c, 6, rq0.temp, nb, memkind) || !fetch_out(c, 7, rq0.hum, nb, memkind) ||
-        !fetch_out(c, 8, rq0.hum2, nb, memkind) || !fetch_out(c, 9, rq0.dd, nb, memkind))
-      return 0;
   }
   MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, 5 * sizeof(u64) * (size_t)nlev, hipMemcpyDeviceToHost, c->stream));
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
+  if (!st.finish())
+    return 0;
   derived_flags(pinned_counts(c), nlev, n, rq0, fdef_ff, fdef_temp, fdef_hum, fdef_hum2, fdef_dd);
   return 1;
 }
@@ -2114,9 +1834,7 @@ int mifc_hlevel_derived_batch(mifc_ctx* c, int nx, int ny, int nlev, const float
                               const int* fdef_wind, const int* fdef_thermo, int* fdef_ff, int* fdef_temp, int* fdef_hum, int* fdef_hum2, int* fdef_dd,
                               float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const DerivedRequest rq = {u, v, t, h, ps, alevel, blevel, ff, temp, hum, hum2, temp_unit, hum_unit, hum2_unit, temp_compute, hum_compute, hum2_compute, dd};
   return derived_sync(c, nx, ny, nlev, rq, fdef_wind, fdef_thermo, fdef_ff, fdef_temp, fdef_hum, fdef_hum2, fdef_dd, undef, memkind);
 }
@@ -2168,9 +1886,7 @@ int mifc_hlevel_derived_levels(mifc_ctx* c, int nx, int ny, int nlev, const floa
                                const float* alevel, const float* blevel, float* ff, float* rh, float* theta, const int* fdef_wind,
                                const int* fdef_thermo, int* fdef_ff, int* fdef_rh, int* fdef_theta, float undef, int memkind)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   const DerivedRequest rq = {u, v, t, q, ps, alevel, blevel, ff, theta, rh, nullptr, "", "", "", 3, 1, 0, nullptr};
   return derived_sync(c, nx, ny, nlev, rq, fdef_wind, fdef_thermo, fdef_ff, fdef_theta, fdef_rh, nullptr, nullptr, undef, memkind);
 }
@@ -2272,9 +1988,7 @@ int mifc_halo_copy_enqueue(mifc_ctx* dst_ctx, float* dst_dev, mifc_ctx* src_ctx,
 #ifdef MIFC_MEASUREMENT_BUILD // libmifc_measure.so only (include/mifc_measure.h)
 int mifc_bench_stream2(mifc_ctx* c, int variant, int blocks, float* dst0, float* dst1, const float* src0, const float* src1, size_t n_floats)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   if (n_floats % 4 != 0)
     return 0;
   MIFC_HIP(c, mifc::launch_stream2(variant, blocks, dst0, dst1, src0, src1, n_floats, c->stream));
@@ -2283,9 +1997,7 @@ int mifc_bench_stream2(mifc_ctx* c, int variant, int blocks, float* dst0, float*
 
 int mifc_diag_division(mifc_ctx* c, const float* a, const float* b, const float* g, float* shared, float* plain, size_t n)
 {
-  if (!c)
-    return 0;
-  enter(c);
+  CTX_OR_FAIL(c);
   MIFC_HIP(c, mifc::launch_division_check(a, b, g, shared, plain, n, c->stream));
   return 1;
 }

@@ -50,17 +50,17 @@ int run_pointwise(mifc_ctx* c, int nx, int ny, PwCall& pc, float* out, int* fdef
   if (nx < 0 || ny < 0 || n64 > 0x7fffffffL || !out)
     return 0;
   const size_t n = (size_t)n64;
-  bool ok = true;
+  Staging st(c, memkind);
   mifc::PwParams& P = pc.P;
   P.n = (int)n;
   P.count = pc.updates_flag ? 1 : 0;
   for (int k = 0; k < pc.nin; ++k) {
     if (!pc.in[k])
       return 0;
-    P.in[k] = stage_in(c, k, pc.in[k], n, memkind, &ok);
+    P.in[k] = st.in(pc.in[k], n);
   }
-  P.out = stage_out(c, 9, out, n, memkind, &ok, P.may_keep != 0);
-  if (!ok || !ensure_levels(c, 1))
+  P.out = st.out(out, n, P.may_keep != 0);
+  if (!st.ok() || !ensure_levels(c, 1))
     return 0;
   P.n_undefined = c->d_counts;
   if (P.count) {
@@ -73,9 +73,8 @@ int run_pointwise(mifc_ctx* c, int nx, int ny, PwCall& pc, float* out, int* fdef
       return 0;
     MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   }
-  if (!fetch_out(c, 9, out, n, memkind))
+  if (!st.finish())
     return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
   if (P.count)
     *fdefined = mifc_classify(pinned_counts(c)[0], (u64)n);
   return 1;
@@ -94,8 +93,8 @@ int fill_undef(mifc_ctx* c, int nx, int ny, float* out, int* fdefined, float und
 }
 
 // Per-cell reduction over `nfields` member fields.  Host
-// members are staged next to each other in scratch slot 0; the table of member
-// pointers and the per-member flags live in slot 8.
+// members are staged next to each other in one scratch block; past 64 members
+// the table of member pointers and the per-member flags live in a second one.
 int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const float* const* fields, const int* member_flags, int nfields, float* out,
                  int* fdefined_out, int memkind, bool may_keep)
 {
@@ -115,12 +114,14 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
     c->err = "out of host memory";
     return 0;
   }
+  Staging st(c, memkind);
   if (memkind == MIFC_MEM_HOST) {
-    const size_t stride = (n + 3) & ~size_t(3); // keeps every staged member 16-byte aligned
-    if (nfields > 0 && !ensure_slot(c, 0, (size_t)nfields * stride * sizeof(float)))
+    const size_t stride = align_up(n, 4); // keeps every staged member 16-byte aligned
+    float* members = nfields > 0 ? static_cast<float*>(st.scratch((size_t)nfields * stride * sizeof(float))) : nullptr;
+    if (!st.ok())
       return 0;
     for (int j = 0; j < nfields; ++j) {
-      float* d = static_cast<float*>(c->slot[0]) + (size_t)j * stride;
+      float* d = members + (size_t)j * stride;
       MIFC_HIP(c, hipMemcpyAsync(d, fields[j], n * sizeof(float), hipMemcpyHostToDevice, c->stream));
       table[(size_t)j] = d;
     }
@@ -128,11 +129,13 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
     for (int j = 0; j < nfields; ++j)
       table[(size_t)j] = fields[j];
   }
-  bool ok = true;
-  P.out = stage_out(c, 9, out, n, memkind, &ok, may_keep);
-  const size_t table_bytes = ((size_t)nfields * sizeof(float*) + 15) & ~size_t(15);
+  P.out = st.out(out, n, may_keep);
+  const size_t table_bytes = align_up((size_t)nfields * sizeof(float*), 16);
   const bool inline_table = nfields <= 64; // pointers and flags ride in the kernel arguments
-  if (!ok || !ensure_levels(c, 1) || (!inline_table && !ensure_slot(c, 8, table_bytes + (size_t)nfields + 16)))
+  if (!st.ok() || !ensure_levels(c, 1))
+    return 0;
+  char* d_table = inline_table ? nullptr : static_cast<char*>(st.scratch(table_bytes + (size_t)nfields + 16));
+  if (!st.ok())
     return 0;
   P.n_inline = inline_table ? 1 : 0;
   P.has_member_flags = member_flags ? 1 : 0;
@@ -142,18 +145,18 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
       P.flags_inline[j] = member_flags ? (unsigned char)member_flags[j] : 0;
     }
   } else if (nfields > 0) {
-    MIFC_HIP(c, hipMemcpyAsync(c->slot[8], table.data(), (size_t)nfields * sizeof(float*), hipMemcpyHostToDevice, c->stream));
+    MIFC_HIP(c, hipMemcpyAsync(d_table, table.data(), (size_t)nfields * sizeof(float*), hipMemcpyHostToDevice, c->stream));
     if (member_flags) {
       for (int j = 0; j < nfields; ++j)
         flags[(size_t)j] = (unsigned char)member_flags[j];
-      MIFC_HIP(c, hipMemcpyAsync(static_cast<char*>(c->slot[8]) + table_bytes, flags.data(), (size_t)nfields, hipMemcpyHostToDevice, c->stream));
+      MIFC_HIP(c, hipMemcpyAsync(d_table + table_bytes, flags.data(), (size_t)nfields, hipMemcpyHostToDevice, c->stream));
     }
   }
   P.n = (int)n;
   P.first = 0;
   P.nfields = nfields;
-  P.fields = inline_table ? nullptr : static_cast<const float* const*>(c->slot[8]);
-  P.member_flags = (member_flags && !inline_table) ? reinterpret_cast<const unsigned char*>(static_cast<char*>(c->slot[8]) + table_bytes) : nullptr;
+  P.fields = reinterpret_cast<const float* const*>(d_table);
+  P.member_flags = (member_flags && !inline_table) ? reinterpret_cast<const unsigned char*>(d_table + table_bytes) : nullptr;
   P.vector_ok = (reinterpret_cast<size_t>(P.out) & 15u) == 0;
   for (int j = 0; j < nfields; ++j)
     P.vector_ok = P.vector_ok && (reinterpret_cast<size_t>(table[(size_t)j]) & 15u) == 0;
@@ -163,17 +166,11 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
   MIFC_HIP(c, hipMemsetAsync(c->d_counts, 0, sizeof(u64), c->stream));
   MIFC_LAUNCH(c, mifc::launch_ensemble(P, c->stream));
   MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  if (!fetch_out(c, 9, out, n, memkind))
+  if (!st.finish()) // also: `table` and `flags` were read by their copies
     return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream)); // also: `table` and `flags` were read by their copies
   *fdefined_out = mifc_classify(pinned_counts(c)[0], (u64)n);
   return 1;
 }
-
-#define CTX_OR_FAIL(c) \
-  if (!(c))            \
-    return 0;          \
-  mifc_host::enter(c)
 
 } // namespace
 
@@ -470,9 +467,9 @@ int mifc_cvtemp(mifc_ctx* c, int nx, int ny, const float* tinp, int compute, flo
   const size_t n = (size_t)nx * (size_t)ny;
   if (compute == 3 || compute == 4) {
     // "convert only if the input seems to be in the other unit" (:1639-1660): mean of the defined cells
-    bool ok = true;
-    const float* d_in = stage_in(c, 0, tinp, n, memkind, &ok);
-    if (!ok || !ensure_levels(c, 1) || !pinned_acquire(c))
+    Staging st(c, memkind); // for the mean only: the conversion below stages the field again, into the same slot
+    const float* d_in = st.in(tinp, n);
+    if (!st.ok() || !ensure_levels(c, 1) || !pinned_acquire(c))
       return 0;
     MIFC_HIP(c, hipMemsetAsync(c->d_counts + 1, 0, 2 * sizeof(u64), c->stream));
     MIFC_LAUNCH(c, mifc::launch_mean_defined(d_in, (int)n, *fdefined == MIFC_ALL_DEFINED, undef, reinterpret_cast<double*>(c->d_counts + 1),
@@ -565,12 +562,14 @@ int mifc_values2classes(mifc_ctx* c, int nx, int ny, const float* fvalue, float*
   if (nvalues < 2 || !values) // :2476
     return 0;
   // the class limits are a host vector in the reference; they always come from the host here too
-  if (!ensure_slot(c, 8, (size_t)nvalues * sizeof(float)))
+  Staging st(c, memkind);
+  float* d_values = static_cast<float*>(st.scratch((size_t)nvalues * sizeof(float)));
+  if (!st.ok())
     return 0;
-  MIFC_HIP(c, hipMemcpyAsync(c->slot[8], values, (size_t)nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  MIFC_HIP(c, hipMemcpyAsync(d_values, values, (size_t)nvalues * sizeof(float), hipMemcpyHostToDevice, c->stream));
   MIFC_HIP(c, hipStreamSynchronize(c->stream)); // `values` may be a temporary of the caller
   PwCall pc = pw_call(mifc::PW_CLASSES, 0, 1, fdefined, undef);
-  pc.P.values = static_cast<const float*>(c->slot[8]);
+  pc.P.values = d_values;
   pc.P.nvalues = nvalues;
   pc.in[0] = fvalue;
   return run_pointwise(c, nx, ny, pc, fclass, fdefined, memkind);
@@ -587,29 +586,30 @@ int mifc_shapiro2_filter(mifc_ctx* c, int nx, int ny, const float* field, float*
   const size_t n = (size_t)nx * (size_t)ny;
   if (n > 0x7fffffffu)
     return 0;
-  bool ok = true;
-  const float* d_in = stage_in(c, 0, field, n, memkind, &ok);
-  float* d_out = stage_out(c, 5, fsmooth, n, memkind, &ok);
+  Staging st(c, memkind);
+  const float* d_in = st.in(field, n);
+  float* d_out = st.out(fsmooth, n);
   const bool all = (*fdefined == MIFC_ALL_DEFINED);
-  if (!ok || !ensure_slot(c, 8, n * sizeof(float)))
+  float* d_sweep = static_cast<float*>(st.scratch(n * sizeof(float)));
+  if (!st.ok())
     return 0;
   {
     // the four sweeps in one launch; it needs source and destination to be different arrays, so an
     // in-place call goes through the scratch field and is copied back
     // MIFC_SHAPIRO_FUSED=0: the four-launch path (A/B measurements, tests)
-    float* d_dst = (d_out != d_in) ? d_out : static_cast<float*>(c->slot[8]);
+    float* d_dst = (d_out != d_in) ? d_out : d_sweep;
     if (mifc::env().shapiro_fused && mifc::shapiro2_fused_supported(nx, ny, d_in, d_dst)) {
       MIFC_LAUNCH(c, mifc::launch_shapiro2_fused(nx, ny, all ? 1 : 0, undef, d_in, d_dst, c->stream));
       if (d_dst != d_out)
         MIFC_HIP(c, hipMemcpyAsync(d_out, d_dst, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      if (!fetch_out(c, 5, fsmooth, n, memkind))
+      if (!st.finish())
         return 0;
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
       *fdefined = MIFC_ALL_DEFINED;
       return 1;
     }
   }
-  if (!all && !ensure_slot(c, 9, 2 * n))
+  unsigned char* d_masks = all ? nullptr : static_cast<unsigned char*>(st.scratch(2 * n));
+  if (!st.ok())
     return 0;
   if (d_out != d_in)
     MIFC_HIP(c, hipMemcpyAsync(d_out, d_in, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -619,13 +619,12 @@ int mifc_shapiro2_filter(mifc_ctx* c, int nx, int ny, const float* field, float*
   P.all_defined = all ? 1 : 0;
   P.undef = undef;
   P.f1 = d_out;
-  P.f2 = static_cast<float*>(c->slot[8]);
-  P.mask_x = all ? nullptr : static_cast<unsigned char*>(c->slot[9]);
-  P.mask_y = all ? nullptr : static_cast<unsigned char*>(c->slot[9]) + n;
+  P.f2 = d_sweep;
+  P.mask_x = d_masks;
+  P.mask_y = all ? nullptr : d_masks + n;
   MIFC_LAUNCH(c, mifc::launch_shapiro2(P, c->stream));
-  if (!fetch_out(c, 5, fsmooth, n, memkind))
+  if (!st.finish())
     return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
   *fdefined = MIFC_ALL_DEFINED;
   return 1;
 }

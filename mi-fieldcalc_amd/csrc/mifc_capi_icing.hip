@@ -14,12 +14,6 @@ namespace {
 
 const int ICING_NIN = 11;
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
-{
-  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-  return pa < pb + bbytes && pb < pa + abytes;
-}
-
 // fdefined[nlev] in/out.  Returns 1 on success, 0 for the reference's `false` (c->err empty) or a refusal / HIP failure
 // (c->err says which).  Nothing is written unless every check passed.
 int icing_run(mifc_ctx* c, const char* fn, int model, int nlev, int nx, int ny, const float* const* in, unsigned shared_mask, float vs, float alpha,
@@ -79,7 +73,7 @@ int icing_run(mifc_ctx* c, const char* fn, int model, int nlev, int nx, int ny, 
     P.br_cos2[k] = C.br_cos2[k];
   }
 
-  // slot 12: counts (u64 [nlev]), level factors (double [number], only past the kernel-argument table), flags (uchar [nlev])
+  // one scratch block: counts (u64 [nlev]), level factors (double [number], only past the kernel-argument table), flags (uchar [nlev])
   const bool buf = C.number > mifc::ICING_KARG_LEVELS;
   const size_t tab_bytes = buf ? (size_t)C.number * sizeof(double) : 0;
   const size_t cnt_bytes = (size_t)nlev * sizeof(u64);
@@ -93,39 +87,33 @@ int icing_run(mifc_ctx* c, const char* fn, int model, int nlev, int nx, int ny, 
   }
   for (int l = 0; l < nlev; ++l)
     host[tab_bytes + (size_t)l] = fdefined[l] == MIFC_ALL_DEFINED ? 1 : 0;
-  if (!ensure_slot(c, 12, cnt_bytes + host.size()))
+  Staging st(c, memkind);
+  unsigned char* d_tab = static_cast<unsigned char*>(st.scratch(cnt_bytes + host.size()));
+  if (!st.ok())
     return 0;
-  unsigned char* s12 = static_cast<unsigned char*>(c->slot[12]);
-  P.n_undefined = reinterpret_cast<u64*>(s12);
-  P.lev_buf = buf ? reinterpret_cast<const double*>(s12 + cnt_bytes) : nullptr;
-  P.all_defined = s12 + cnt_bytes + tab_bytes;
+  P.n_undefined = reinterpret_cast<u64*>(d_tab);
+  P.lev_buf = buf ? reinterpret_cast<const double*>(d_tab + cnt_bytes) : nullptr;
+  P.all_defined = d_tab + cnt_bytes + tab_bytes;
 
-  bool ok = true;
   for (int k = 0; k < ICING_NIN; ++k) {
     const bool shared = (shared_mask >> k) & 1u;
-    P.in[k] = stage_in(c, k, in[k], shared ? cells : n, memkind, &ok);
+    P.in[k] = st.in(in[k], shared ? cells : n);
     P.in_stride[k] = shared ? 0 : (long)cells;
   }
-  P.out = stage_out(c, 11, out, n, memkind, &ok);
-  if (!ok)
+  P.out = st.out(out, n);
+  if (!st.ok())
     return 0;
-  MIFC_HIP(c, hipMemcpyAsync(s12 + cnt_bytes, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-  MIFC_HIP(c, hipMemsetAsync(s12, 0, cnt_bytes, c->stream));
+  MIFC_HIP(c, hipMemcpyAsync(d_tab + cnt_bytes, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+  MIFC_HIP(c, hipMemsetAsync(d_tab, 0, cnt_bytes, c->stream));
   MIFC_LAUNCH(c, mifc::launch_vessel_icing(P, c->stream));
   std::vector<u64> counts((size_t)nlev);
-  MIFC_HIP(c, hipMemcpyAsync(counts.data(), s12, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (!fetch_out(c, 11, out, n, memkind))
+  MIFC_HIP(c, hipMemcpyAsync(counts.data(), d_tab, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (!st.finish())
     return 0;
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
   for (int l = 0; l < nlev; ++l)
     fdefined[l] = mifc_classify(counts[(size_t)l], (u64)cells); // :335, :703
   return 1;
 }
-
-#define CTX_OR_FAIL(c) \
-  if (!(c))            \
-    return 0;          \
-  mifc_host::enter(c)
 
 } // namespace
 

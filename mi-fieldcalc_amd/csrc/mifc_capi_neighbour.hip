@@ -117,39 +117,33 @@ int nb_run(mifc_ctx* c, NbPlan& p, int nlev, const float* field, float* fres, in
   mifc::NeighbourParams& P = p.P;
   const size_t n = (size_t)P.nx * (size_t)P.ny * (size_t)nlev;
   if (p.kind != 0) {
-    bool ok = true;
+    Staging st(c, memkind);
     P.nlev = nlev;
     P.level_stride = (long)P.nx * (long)P.ny;
     P.undef = undef;
-    P.in = stage_in(c, 0, field, n, memkind, &ok);
+    P.in = st.in(field, n);
     // host fields: cells that no block covers must come back as the caller had them
-    P.out = stage_out(c, 9, fres, n, memkind, &ok, p.keeps_cells);
-    if (!ok)
+    P.out = st.out(fres, n, p.keeps_cells);
+    if (!st.ok())
       return 0;
     if (p.kind == 2) {
-      if (!ensure_slot(c, 8, (size_t)nlev * P.ny * mifc::neighbour_words(P.nx) * sizeof(u64)))
+      P.bits = static_cast<u64*>(st.scratch((size_t)nlev * P.ny * mifc::neighbour_words(P.nx) * sizeof(u64)));
+      if (!st.ok())
         return 0;
-      P.bits = static_cast<u64*>(c->slot[8]);
       MIFC_LAUNCH(c, mifc::launch_neighbour_box(P, c->stream));
     } else if (p.kind == 1) {
       MIFC_LAUNCH(c, mifc::launch_neighbour_threshold(P, c->stream));
     } else {
       MIFC_LAUNCH(c, mifc::launch_neighbour_functions(P, c->stream));
     }
-    if (!fetch_out(c, 9, fres, n, memkind))
+    if (!st.finish())
       return 0;
-    MIFC_HIP(c, hipStreamSynchronize(c->stream));
   }
   if (!p.flag_unchanged)
     for (int l = 0; l < nflags; ++l)
       fdefined[l] = MIFC_SOME_DEFINED; // :2928, :2988
   return 1;
 }
-
-#define CTX_OR_FAIL(c) \
-  if (!(c))            \
-    return 0;          \
-  mifc_host::enter(c)
 
 } // namespace
 

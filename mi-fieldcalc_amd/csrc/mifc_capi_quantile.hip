@@ -13,27 +13,11 @@ using namespace mifc_host;
 
 namespace {
 
-bool overlaps(const void* a, const void* b, size_t bytes)
-{
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa == pb || (pa < pb + bytes && pb < pa + bytes);
-}
-
 int refuse(mifc_ctx* c, const std::string& why)
 {
   c->err = "mifc_ensembleQuantiles: " + why;
   return 0;
 }
-
-size_t align16(size_t b)
-{
-  return (b + 15) & ~size_t(15);
-}
-
-#define CTX_OR_FAIL(c) \
-  if (!(c))            \
-    return 0;          \
-  mifc_host::enter(c)
 
 } // namespace
 
@@ -104,6 +88,7 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
 
   // device-side arrays of the launch
   const bool host = memkind == MIFC_MEM_HOST;
+  Staging st(c, memkind); // blocks only: members and outputs are sub-allocated and copied chunk by chunk below
   size_t lev_chunk = (size_t)nlev, cell_chunk = cells, S = 0;
   std::vector<int> alias; // device memory: outputs that overlap a member, computed into scratch and copied back
   if (host) {
@@ -116,28 +101,31 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
       lev_chunk = 1;
       cell_chunk = std::max((size_t)1, budget / per_cell);
     }
-    S = (lev_chunk * cell_chunk + 63) & ~size_t(63);
-    if ((nmem > 0 && !ensure_slot(c, 0, (size_t)nmem * S * sizeof(float))) || !ensure_slot(c, 1, (size_t)nq * S * sizeof(float)))
+    S = align_up(lev_chunk * cell_chunk, 64);
+    const float* d_mem = nmem > 0 ? static_cast<const float*>(st.scratch((size_t)nmem * S * sizeof(float))) : nullptr;
+    float* d_out = static_cast<float*>(st.scratch((size_t)nq * S * sizeof(float)));
+    if (!st.ok())
       return 0;
     for (int j = 0; j < nmem; ++j)
-      mem[(size_t)j] = static_cast<const float*>(c->slot[0]) + (size_t)j * S;
+      mem[(size_t)j] = d_mem + (size_t)j * S;
     for (int q = 0; q < nq; ++q)
-      out[(size_t)q] = static_cast<float*>(c->slot[1]) + (size_t)q * S;
+      out[(size_t)q] = d_out + (size_t)q * S;
   } else {
     for (int q = 0; q < nq; ++q)
       for (int j = 0; j < nmem; ++j)
-        if (overlaps(fres[q], fields[j], bytes)) {
+        if (overlaps(fres[q], bytes, fields[j], bytes)) { // (bytes > 0 here: an empty grid has returned above)
           alias.push_back(q);
           break;
         }
-    if (!alias.empty() && !ensure_slot(c, 1, alias.size() * bytes))
+    float* d_alias = alias.empty() ? nullptr : static_cast<float*>(st.scratch(alias.size() * bytes));
+    if (!st.ok())
       return 0;
     for (int j = 0; j < nmem; ++j)
       mem[(size_t)j] = fields[j];
     for (int q = 0; q < nq; ++q)
       out[(size_t)q] = fres[q];
     for (size_t k = 0; k < alias.size(); ++k)
-      out[(size_t)alias[k]] = static_cast<float*>(c->slot[1]) + k * total;
+      out[(size_t)alias[k]] = d_alias + k * total;
   }
 
   mifc::QuantileParams P;
@@ -159,9 +147,9 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
     for (int l = 0; l < nlev; ++l)
       P.all_inline[l] = bits[(size_t)l];
   } else {
-    // slot 8: member pointers | output pointers | percentiles | ALL_DEFINED bits, uploaded once per call
-    const size_t o_out = align16((size_t)nmem * sizeof(float*)), o_p = o_out + align16((size_t)nq * sizeof(float*));
-    const size_t o_bits = o_p + align16((size_t)nq * sizeof(float)), tab_bytes = o_bits + bits.size() * sizeof(u64);
+    // one scratch block: member pointers | output pointers | percentiles | ALL_DEFINED bits, uploaded once per call
+    const size_t o_out = align_up((size_t)nmem * sizeof(float*), 16), o_p = o_out + align_up((size_t)nq * sizeof(float*), 16);
+    const size_t o_bits = o_p + align_up((size_t)nq * sizeof(float), 16), tab_bytes = o_bits + bits.size() * sizeof(u64);
     try {
       tab.assign(tab_bytes, 0);
     } catch (...) {
@@ -173,9 +161,9 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
     std::memcpy(tab.data() + o_out, out.data(), (size_t)nq * sizeof(float*));
     std::memcpy(tab.data() + o_p, percentiles, (size_t)nq * sizeof(float));
     std::memcpy(tab.data() + o_bits, bits.data(), bits.size() * sizeof(u64));
-    if (!ensure_slot(c, 8, tab_bytes))
+    unsigned char* d = static_cast<unsigned char*>(st.scratch(tab_bytes));
+    if (!st.ok())
       return 0;
-    unsigned char* d = static_cast<unsigned char*>(c->slot[8]);
     MIFC_HIP(c, hipMemcpyAsync(d, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     P.tab.mem = reinterpret_cast<const float* const*>(d);
     P.tab.out = reinterpret_cast<float* const*>(d + o_out);
@@ -217,7 +205,8 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
   }
   std::vector<u64> counts((size_t)nlev);
   MIFC_HIP(c, hipMemcpyAsync(counts.data(), c->d_counts, (size_t)nlev * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  MIFC_HIP(c, hipStreamSynchronize(c->stream)); // also: `tab` was read by its copy
+  if (!st.finish()) // nothing to copy back (the chunks went as they were done): the synchronisation; also, `tab` was read by its copy
+    return 0;
   for (int l = 0; l < nlev; ++l)
     fdefined_out[l] = nmem == 0 ? MIFC_NONE_DEFINED : mifc_classify(counts[(size_t)l], (u64)cells);
   return 1;

@@ -1,6 +1,7 @@
 // mifc_ctx.h -- internals shared by the host-side translation units of the C
-// ABI (mifc_capi.hip: hot path and stencil family; mifc_capi_catalogue.hip: the
-// rest of the pointwise catalogue and the ensemble reductions).  Not installed.
+// ABI (mifc_capi*.hip, mifc_slab.hip, mifc_graph.hip, ...): the context, the
+// per-call staging of host fields and the small helpers every entry point
+// uses.  Implemented in mifc_ctx.hip.  Not installed.
 #ifndef MIFC_CTX_H
 #define MIFC_CTX_H
 
@@ -21,10 +22,14 @@ struct mifc_ctx
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
-  // grow-only device scratch slots for staged host fields
-  static const int NSLOT = 13;
-  void* slot[NSLOT] = {nullptr};
-  size_t slot_bytes[NSLOT] = {0};
+  // grow-only device scratch slots, handed out in call order by mifc_host::Staging (the only code that touches them)
+  struct Slot
+  {
+    void* ptr;
+    size_t bytes;
+  };
+  std::vector<Slot> slot;
+  size_t slot_cursor = 0; // the next free slot of the running call; 0 between calls
   // per-level flags / counters
   unsigned char* d_flags = nullptr; // 2 * cap_lev bytes (wind | thermo, or just one set)
   u64* d_counts = nullptr;          // 5 * cap_lev
@@ -115,7 +120,11 @@ inline void enter(mifc_ctx* c)
 #define MIFC_LAUNCH(c, call) MIFC_HIP(c, call)
 #endif
 
-bool ensure_slot(mifc_ctx* c, int s, size_t bytes);
+#define CTX_OR_FAIL(c) \
+  if (!(c))            \
+    return 0;          \
+  mifc_host::enter(c)
+
 bool ensure_levels(mifc_ctx* c, size_t nlev);
 // scratch for the per-workgroup counts of a counted one-shot launch over n cells (nullptr below the size where it pays)
 unsigned int* partials_for(mifc_ctx* c, size_t n_cells, int* cap);
@@ -125,10 +134,64 @@ bool scratch_release(mifc_ctx* c);
 u64* pinned_counts(mifc_ctx* c);
 unsigned char* pinned_flags(mifc_ctx* c);
 float* pinned_ab(mifc_ctx* c);
-// Brings a field to the device if the caller handed a host pointer (slot s of the context's scratch).
-const float* stage_in(mifc_ctx* c, int s, const float* p, size_t n, int memkind, bool* ok);
-float* stage_out(mifc_ctx* c, int s, float* p, size_t n, int memkind, bool* ok, bool preload = false);
-bool fetch_out(mifc_ctx* c, int s, float* p, size_t n, int memkind);
+
+// The device homes of one call's host fields.  Every staged field and every scratch block takes the
+// context's next slot (each slot an allocation of its own that only grows); the destructor hands the
+// slots back.  So a driver or an entry point called while a caller's Staging is alive continues after
+// the caller's slots (the level-by-level fallback of mifc_stencil_levels_ex calls entry points with the
+// batch staged, which is why enter() does not start the slots again), and calls one after the other use
+// the same ones.  A pointer handed out is good until the object goes.  A null pointer, MIFC_MEM_DEVICE
+// memory and a host field held by mifc_hold_field pass through and take no slot.
+class Staging
+{
+public:
+  Staging(mifc_ctx* c, int memkind) : c_(c), memkind_(memkind), base_(c->slot_cursor) {}
+  ~Staging() { c_->slot_cursor = base_; }
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  // uploads n floats (asynchronously, on the context's stream) and returns where they are on the device
+  const float* in(const float* p, size_t n);
+  // a device home for n floats that finish() copies back to p; preload: start from the caller's content
+  // (operators that leave cells unwritten)
+  float* out(float* p, size_t n, bool preload = false);
+  // a block for intermediates, tables or a driver's own sub-allocated staging, whatever the memkind
+  void* scratch(size_t bytes);
+  // false once a step has failed (the context's error says which); the pointers returned since are null
+  bool ok() const { return ok_; }
+  // end of the call: the outputs back to the host, then ONE synchronisation of the stream
+  bool finish();
+
+private:
+  void* take(size_t bytes);
+  struct Out
+  {
+    float* host;
+    const void* dev;
+    size_t n;
+  };
+  static const int MAX_OUT = 8;
+  mifc_ctx* c_;
+  int memkind_;
+  size_t base_; // the context's cursor when the call began
+  bool ok_ = true;
+  int n_out_ = 0;
+  Out outs_[MAX_OUT];
+};
+
+// mifc_destroy
+void free_slots(mifc_ctx* c);
+
+inline size_t align_up(size_t bytes, size_t pow2)
+{
+  return (bytes + pow2 - 1) & ~(pow2 - 1);
+}
+
+// Do [a, a + abytes) and [b, b + bbytes) share a byte?  (Two empty ranges never do, not even at the same address.)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
+{
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return pa < pb + bbytes && pb < pa + abytes;
+}
 
 // MetConstants.h:43-53 (host copies, evaluated like the reference does on the CPU)
 const float K_CP = 1004.f, K_T0 = 273.15f;

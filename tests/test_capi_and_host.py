@@ -365,6 +365,22 @@ def test_environment_is_read_in_one_place_only():
             assert "getenv" not in code, f
 
 
+def test_scratch_slots_are_touched_by_the_staging_object_only():
+    """The context's scratch slots are handed out per call by mifc_host::Staging (csrc/mifc_ctx.h, mifc_ctx.hip): no
+    other file indexes them or names the helpers that took a slot number, and CTX_OR_FAIL is defined once."""
+    csrc = os.path.join(ROOT, "mi-fieldcalc_amd", "csrc")
+    defines = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        defines += text.count("#define CTX_OR_FAIL")
+        if f not in ("mifc_ctx.h", "mifc_ctx.hip"):
+            for word in ("->slot[", "slot_bytes", "NSLOT", "stage_in(", "stage_out(", "fetch_out(", "ensure_slot("):
+                assert word not in text, (f, word)
+    assert defines == 1
+
+
 def test_choose_placement_keeps_the_fastest_candidate():
     """placement.choose_placement: every candidate is allocated and probed once, the fastest is returned,
     the report names it; the losers are released."""
