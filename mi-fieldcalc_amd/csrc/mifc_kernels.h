@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mifc_env.h"
+#include "mifc_stencil_limits.h" // the launch-size thresholds the stencil launchers share
 
 namespace mifc {
 

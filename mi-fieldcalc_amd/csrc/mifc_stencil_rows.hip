@@ -614,7 +614,7 @@ hipError_t launch_scalar_rows(const StencilParams& prm, hipStream_t stream, bool
   rp.R = 8;
   const int forced_r = env().scalar_rows_r; // -1: not set
   if (forced_r < 0) {
-    while (rp.R > 2 && (long)prm.nlev * ((ny - 2 + rp.R - 1) / rp.R) * rp.nwc < 2048) // waves of the launch
+    while (rp.R > 2 && (long)prm.nlev * ((ny - 2 + rp.R - 1) / rp.R) * rp.nwc < kSmallLaunchWaves) // waves of the launch
       rp.R /= 2;
   } else if (forced_r > 0) {
     rp.R = forced_r; // A/B measurements
@@ -627,7 +627,7 @@ hipError_t launch_scalar_rows(const StencilParams& prm, hipStream_t stream, bool
   rp.uB = rp.nbands;
   rp.uW = rp.nwc;
   const long n_logical = (long)rp.uL * rp.uB * rp.uW;
-  if (n_logical > 0x3fffffffL)
+  if (n_logical > kUnitIndexLimit)
     return hipSuccess;
   rp.n_logical = (int)n_logical;
   rp.per_xcd = (rp.n_logical + 7) / 8;
@@ -650,7 +650,7 @@ hipError_t launch_scalar_rows(const StencilParams& prm, hipStream_t stream, bool
   // two levels of any size: their row-walking workgroups would be single waves holding a 48-KiB tile of map
   // factors, three to a CU
   // (MIFC_LEVELWALK_MIN_UNITS, the tests' switch, sends launches of any size to the level-walking forms)
-  if (forced_r < 0 && ((env().levelwalk_min_units <= 0 && (long)prm.nlev * ((ny - 2 + 7) / 8) * rp.nwc < 2048) || prm.nlev <= 2)) {
+  if (forced_r < 0 && ((env().levelwalk_min_units <= 0 && (long)prm.nlev * ((ny - 2 + 7) / 8) * rp.nwc < kSmallLaunchWaves) || prm.nlev <= 2)) {
     rp.uB = (ny - 2 + 3) / 4;
     rp.uW = (nx + 255) / 256;
     const long units = (long)prm.nlev * rp.uB * rp.uW;
@@ -658,7 +658,7 @@ hipError_t launch_scalar_rows(const StencilParams& prm, hipStream_t stream, bool
       grid = (int)units;
       form = 0;
       // one big level with tests: the workgroups' counts by plain stores + one small launch (StencilParams::partials)
-      if (check && prm.partials && prm.n_undefined && (long)rp.uB * rp.uW >= 2048 && units <= prm.partials_cap)
+      if (check && prm.partials && prm.n_undefined && (long)rp.uB * rp.uW >= kPartialCountUnitsPerLevel && units <= prm.partials_cap)
         rp.partials = prm.partials;
     }
   }
@@ -670,11 +670,11 @@ hipError_t launch_scalar_rows(const StencilParams& prm, hipStream_t stream, bool
   // arithmetic with each other's memory time.  So only the light ones take this form by default; with
   // MIFC_LEVELWALK_MIN_UNITS set (tests) every operator does.
   const bool light = (op == ST_GRAD_X || op == ST_GRAD_Y);
-  if (form != 0 && forced_r < 0 && env().levelwalk && (light || env().levelwalk_min_units > 0) && prm.nlev >= 3 && (long)nx * ny < 0x7fffffffL) {
+  if (form != 0 && forced_r < 0 && env().levelwalk && (light || env().levelwalk_min_units > 0) && prm.nlev >= kLevelWalkMinLevels && (long)nx * ny < 0x7fffffffL) {
     const int target = prm.nlev >= 48 ? 6 : 8; // levels per chunk, then balanced
     const int nchunks = (prm.nlev + target - 1) / target;
     const long tiles = (long)((ny - 2 + LW_ROWS - 1) / LW_ROWS) * ((nx + 255) / 256);
-    if (tiles * nchunks >= (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : 768) && tiles * nchunks <= 0x3fffffffL) {
+    if (tiles * nchunks >= (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : kLevelWalkMinUnits) && tiles * nchunks <= kUnitIndexLimit) {
       rp.uB = (ny - 2 + LW_ROWS - 1) / LW_ROWS;
       rp.uW = (nx + 255) / 256;
       rp.wpb = (prm.nlev + nchunks - 1) / nchunks;

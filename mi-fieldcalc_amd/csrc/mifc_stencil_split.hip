@@ -706,7 +706,7 @@ void launch_op(const SRowsParams& rp, const SplitShape& sh, bool check, int grid
 // tiles x level chunks of the launch
 bool plan(const SplitShape& sh, int nx, int ny, int nlev, int* levels_per_chunk, long* units)
 {
-  if (nlev < 3 || (long)nx * ny >= 0x7fffffffL)
+  if (nlev < kLevelWalkMinLevels || (long)nx * ny >= 0x7fffffffL)
     return false;
   const int target = sh.lg > 0 ? sh.lg : (nlev >= 48 ? 6 : 8); // levels per chunk; the chunks are then balanced
   const int nchunks = (nlev + target - 1) / target;
@@ -714,7 +714,7 @@ bool plan(const SplitShape& sh, int nx, int ny, int nlev, int* levels_per_chunk,
   const long tiles = (long)((ny - 2 + sh.tr - 1) / sh.tr) * ((nx + 255) / 256);
   *levels_per_chunk = lpc;
   *units = tiles * ((nlev + lpc - 1) / lpc);
-  return *units <= 0x3fffffffL;
+  return *units <= kUnitIndexLimit;
 }
 
 } // namespace
@@ -732,7 +732,7 @@ bool scalar_split_applies(int op, int nx, int ny, int nlev, bool check, float un
   long units;
   if (!shape_exists(sh) || !plan(sh, nx, ny, nlev, &lpc, &units))
     return false;
-  return units >= (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : 768);
+  return units >= (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : kLevelWalkMinUnits);
 }
 
 hipError_t launch_scalar_split(int op, SRowsParams& rp, bool check, hipStream_t stream)
@@ -750,7 +750,7 @@ hipError_t launch_scalar_split(int op, SRowsParams& rp, bool check, hipStream_t 
   const int grid = rp.per_xcd * 8;
   // big levels with tests: counts by plain stores (rp.partials[level][tile], set by the caller where its buffer is large
   // enough), added up by the caller behind this launch
-  if (!(check && rp.partials && rp.n_undefined && (long)rp.uB * rp.uW >= 2048 && (long)rp.uB * rp.uW * rp.nlev <= rp.partials_cap))
+  if (!(check && rp.partials && rp.n_undefined && (long)rp.uB * rp.uW >= kPartialCountUnitsPerLevel && (long)rp.uB * rp.uW * rp.nlev <= rp.partials_cap))
     rp.partials = nullptr;
   switch (op) {
   case ST_GRAD_X:
@@ -788,7 +788,7 @@ hipError_t launch_advection_split(const StencilParams& prm, hipStream_t stream, 
   const int nx = prm.nx, ny = prm.ny_global;
   if (prm.op != ST_ADVECTION || !env().split_roles || !env().levelwalk || env().force_cell_kernel)
     return hipSuccess;
-  if (nx < 8 || ny < 3 || prm.j0 != 0 || prm.ny_local != ny || prm.nlev < 3 || (long)nx * ny >= 0x7fffffffL)
+  if (nx < 8 || ny < 3 || prm.j0 != 0 || prm.ny_local != ny || prm.nlev < kLevelWalkMinLevels || (long)nx * ny >= 0x7fffffffL)
     return hipSuccess;
   if (!prm.f0 || !prm.f1 || !prm.f2 || !prm.xmapr || !prm.ymapr || !prm.out0)
     return hipSuccess;
@@ -804,7 +804,7 @@ hipError_t launch_advection_split(const StencilParams& prm, hipStream_t stream, 
   const SplitShape sh = {TR, NL, PF, 0};
   int lpc;
   long units;
-  if (!plan(sh, nx, ny, prm.nlev, &lpc, &units) || units < (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : 768))
+  if (!plan(sh, nx, ny, prm.nlev, &lpc, &units) || units < (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : kLevelWalkMinUnits))
     return hipSuccess;
   SRowsParams rp{};
   rp.nx = nx;
@@ -831,7 +831,7 @@ hipError_t launch_advection_split(const StencilParams& prm, hipStream_t stream, 
   *handled = true;
   note_form("advection_split");
   const long tiles = (long)rp.uB * rp.uW;
-  if (check && prm.partials && prm.n_undefined && tiles >= 2048 && tiles * prm.nlev <= prm.partials_cap)
+  if (check && prm.partials && prm.n_undefined && tiles >= kPartialCountUnitsPerLevel && tiles * prm.nlev <= prm.partials_cap)
     rp.partials = prm.partials;
   if (ragged) {
     note_form("advection_split_ragged");

@@ -45,6 +45,7 @@
 //     same kernel runs in the same time).
 #include "mifc_device.h"
 #include "mifc_kernels.h"
+#include "mifc_vortdiv_plan.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -63,7 +64,7 @@ struct RowsParams
   int lo, hi;   // owned local rows that are computed: [lo, hi)
   int R;        // rows per band
   int nbands, nwc, nlev;
-  int wpb;             // waves per workgroup (4, 8 or 16): that many levels side by side
+  int wpb;             // waves per workgroup (1, 2, 4 or 8): that many levels side by side
   int uL, uB, uW;      // workgroup-unit counts along (level groups, bands, wave-columns)
   int n_logical;       // uL * uB * uW
   int per_xcd;         // ceil(n_logical / 8)
@@ -1518,144 +1519,170 @@ __global__ __launch_bounds__(64 * (TR + NL)) void vortdiv_split_kernel(const Row
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-struct Tuning
-{
-  int K;     // 0: row-walking kernel (default), 1: one-shot kernel, 2: one-shot tiles with the row reuse in LDS, 3: level-walking tiles
-  int R;     // rows per band
-  int D;     // rows kept in flight beyond the 3-row window (0 or 1)
-  int NT;    // nontemporal stores
-  int V;     // float4 per lane and row (1 or 2): the wave covers 256*V columns
-  int ORDER; // block order, see decode_block()
-  int XCD;   // XCD-aware blockIdx remap
-  int WPB;   // waves per workgroup: 4, 8 or 16 (levels side by side)
-  int ZZ;    // odd bands walk upwards (halo rows meet in L2)
-  int NTI;   // nontemporal loads for the rows of a band that no other band reads
-  int XH;    // measurement build only: skip the halo rows (results are wrong)
-  int XS;    // measurement build only: skip (practically all) stores
-  int PADROWS; // measurement build only: the last PADROWS rows of every level are padding (changes the level stride)
-  int XL;      // measurement build only: skip the field loads (write side alone)
-  int LDSX;    // extra KiB of LDS requested per workgroup: limits the workgroups resident on a CU (occupancy experiments)
-  int STA;     // measurement build only: buffer stores with this cache policy (aux bits)
-  int LG;      // one-shot forms: level-minor unit order in groups of LG levels (0: address order)
-  int RB;      // one-shot tile form: rows per tile (8 or 14)
-};
-
-int tune_value(const char* s, const char* key, int dflt)
-{
-  // finds "KEY=" at the start of the string or after a comma
-  const size_t n = std::strlen(key);
-  for (const char* p = s; p && *p;) {
-    if (std::strncmp(p, key, n) == 0 && p[n] == '=')
-      return std::atoi(p + n + 1);
-    p = std::strchr(p, ',');
-    if (p)
-      ++p;
-  }
-  return dflt;
-}
-
-Tuning current_tuning(int nx)
-{
-  Tuning t = {0, 8, 1, 1, 2, 1, 1, 8, 1, 0, 0, 0, 0, 0, 0, 0, 0, 8}; // R = 6 / WPB = 4 run within 1 % of this but fetch more (halo rows, map factors): HBM traffic 1.13-1.14x vs 1.08x of the minimum
-  // MIFC_VORTDIV_TUNE="R=8,D=1,NT=1,V=2,ORDER=1,XCD=1,WPB=8" -- used by the sweep tool and the tests
-  if (env().has_vortdiv_tune) {
-    const char* s = env().vortdiv_tune;
-    t.K = tune_value(s, "K", t.K);
-    t.R = tune_value(s, "R", t.R);
-    t.D = tune_value(s, "D", t.D);
-    t.NT = tune_value(s, "NT", t.NT);
-    t.V = tune_value(s, "V", t.V);
-    t.ORDER = tune_value(s, "ORDER", t.ORDER);
-    t.XCD = tune_value(s, "XCD", t.XCD);
-    t.WPB = tune_value(s, "WPB", t.WPB);
-    t.ZZ = tune_value(s, "ZZ", t.ZZ);
-    t.NTI = tune_value(s, "NTI", t.NTI);
-    t.LDSX = tune_value(s, "LDSX", t.LDSX);
-    t.LG = tune_value(s, "LG", t.LG);
-    t.RB = tune_value(s, "RB", t.RB);
-#ifdef MIFC_MEASUREMENT_BUILD
-    // knobs that make the kernel compute something else (wrong results by design): they exist in
-    // libmifc_measure.so only, which tools/ load explicitly; the product library has no such code
-    t.XH = tune_value(s, "XH", 0);
-    t.XS = tune_value(s, "XS", 0);
-    t.PADROWS = tune_value(s, "PADROWS", 0);
-    t.XL = tune_value(s, "XL", 0);
-    t.STA = tune_value(s, "STA", 0);
-#endif
-  }
-  if (t.WPB != 1 && t.WPB != 2 && t.WPB != 4 && t.WPB != 8)
-    t.WPB = 4; // the kernel is compiled for workgroups of up to 8 waves
-  if (t.V != 1 && t.V != 2 && t.V != 3)
-    t.V = 2;
-  if (nx <= 256)
-    t.V = 1; // a second 256-column segment would be empty
-  if (t.R < 1)
-    t.R = 1;
-  const int rmax = 32 / t.V; // map-factor tile in LDS: up to 3*V KiB per row (absvort), 96 KiB at most
-  if (t.R > rmax)
-    t.R = rmax;
-  if (t.D < 0)
-    t.D = 0;
-  if (t.D > 1)
-    t.D = 1; // deeper rings (2, 3) were measured -- same time, profiles/r01/experiments/sweep_d.txt -- and are not instantiated
-  return t;
-}
+// KERNEL<CHECK, ...> on the plan's grid (CHECK: some level of the launch has to be tested)
+#define WIND_LAUNCH(KERNEL, ...)                                                                           \
+  do {                                                                                                     \
+    if (chk)                                                                                               \
+      hipLaunchKernelGGL((KERNEL<true, __VA_ARGS__>), dim3(p.grid), dim3(p.block), p.lds, stream, rp);     \
+    else                                                                                                   \
+      hipLaunchKernelGGL((KERNEL<false, __VA_ARGS__>), dim3(p.grid), dim3(p.block), p.lds, stream, rp);    \
+  } while (0)
 
 template <bool CHECK, bool WV, bool WD, bool ABSV, int D, bool NT>
-void launch_v(const RowsParams& rp, const Tuning& t, int grid, hipStream_t stream)
+void launch_v(const RowsParams& rp, const WindPlan& p, hipStream_t stream)
 {
-  const size_t lds = (size_t)rp.R * 1024 * t.V * (ABSV ? 3 : 2) + (size_t)t.LDSX * 1024;
-  if (t.V == 2)
-    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 2>), dim3(grid), dim3(64 * t.WPB), lds, stream, rp);
-  else if (t.V == 3)
-    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 3>), dim3(grid), dim3(64 * t.WPB), lds, stream, rp);
+  if (p.V == 2)
+    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 2>), dim3(p.grid), dim3(p.block), p.lds, stream, rp);
+  else if (p.V == 3)
+    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 3>), dim3(p.grid), dim3(p.block), p.lds, stream, rp);
   else
-    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 1>), dim3(grid), dim3(64 * t.WPB), lds, stream, rp);
+    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, WV, WD, ABSV, D, NT, 1>), dim3(p.grid), dim3(p.block), p.lds, stream, rp);
 }
 
 template <bool CHECK, bool WV, bool WD, bool ABSV>
-void launch_d(const RowsParams& rp, const Tuning& t, int grid, hipStream_t stream)
+void launch_d(const RowsParams& rp, const WindPlan& p, hipStream_t stream)
 {
-  if (!t.NT) { // plain stores: only the default depth is instantiated
-    launch_v<CHECK, WV, WD, ABSV, 1, false>(rp, t, grid, stream);
-    return;
-  }
-  if (!(WV && WD)) { // single-output forms: default depth only (the depth sweep is about the fused kernel)
-    launch_v<CHECK, WV, WD, ABSV, 1, true>(rp, t, grid, stream);
-    return;
-  }
-  if (t.D == 0)
-    launch_v<CHECK, WV, WD, ABSV, 0, true>(rp, t, grid, stream);
+  if (!p.NT)
+    launch_v<CHECK, WV, WD, ABSV, 1, false>(rp, p, stream);
+  else if (p.D == 0)
+    launch_v<CHECK, WV, WD, ABSV, 0, true>(rp, p, stream);
   else
-    launch_v<CHECK, WV, WD, ABSV, 1, true>(rp, t, grid, stream);
+    launch_v<CHECK, WV, WD, ABSV, 1, true>(rp, p, stream);
 }
 
 template <bool CHECK>
-void launch_jacobian(const RowsParams& rp, const Tuning& t, int grid, hipStream_t stream)
-{
-  const size_t lds = (size_t)rp.R * 1024 * t.V * 2;
-  if (t.V == 2)
-    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, true, false, false, 1, true, 2, true>), dim3(grid), dim3(64 * t.WPB), lds, stream, rp);
-  else
-    hipLaunchKernelGGL((vortdiv_rows_kernel<CHECK, true, false, false, 1, true, 1, true>), dim3(grid), dim3(64 * t.WPB), lds, stream, rp);
-}
-
-template <bool CHECK>
-void launch_outputs(const RowsParams& rp, const Tuning& t, int grid, hipStream_t stream)
+void launch_outputs(const RowsParams& rp, const WindPlan& p, hipStream_t stream)
 {
   if (rp.fc)
-    launch_d<CHECK, true, false, true>(rp, t, grid, stream);
+    launch_d<CHECK, true, false, true>(rp, p, stream);
   else if (rp.rv && rp.dv)
-    launch_d<CHECK, true, true, false>(rp, t, grid, stream);
+    launch_d<CHECK, true, true, false>(rp, p, stream);
   else if (rp.rv)
-    launch_d<CHECK, true, false, false>(rp, t, grid, stream);
+    launch_d<CHECK, true, false, false>(rp, p, stream);
   else
-    launch_d<CHECK, false, true, false>(rp, t, grid, stream);
+    launch_d<CHECK, false, true, false>(rp, p, stream);
 }
 
-// when the level-walking form takes over from the row-walking one (measured: profiles/r02/experiments/levelwalk_threshold.txt)
-constexpr int kLevelWalkMinLevels = 3;
-constexpr long kLevelWalkMinUnits = 768;
+// Each of the five takes the shape plan_wind() settled on and only picks the instantiation.
+void launch_rows(const RowsParams& rp, const WindPlan& p, bool jac, bool chk, hipStream_t stream)
+{
+  if (jac && p.V == 2)
+    WIND_LAUNCH(vortdiv_rows_kernel, true, false, false, 1, true, 2, true);
+  else if (jac)
+    WIND_LAUNCH(vortdiv_rows_kernel, true, false, false, 1, true, 1, true);
+  else if (chk)
+    launch_outputs<true>(rp, p, stream);
+  else
+    launch_outputs<false>(rp, p, stream);
+}
+
+void launch_oneshot(const RowsParams& rp, const WindPlan& p, bool jac, bool chk, hipStream_t stream)
+{
+#define ONESHOT(WV, WD)                                       \
+  if (p.NT)                                                   \
+    WIND_LAUNCH(vortdiv_oneshot_kernel, WV, WD, true);        \
+  else                                                        \
+    WIND_LAUNCH(vortdiv_oneshot_kernel, WV, WD, false)
+  if (rp.fc) {
+    WIND_LAUNCH(vortdiv_oneshot_kernel, true, false, true, false, true);
+  } else if (jac) {
+    WIND_LAUNCH(vortdiv_oneshot_kernel, true, false, true, true);
+  } else if (rp.rv && rp.dv) {
+    ONESHOT(true, true);
+  } else if (rp.rv) {
+    ONESHOT(true, false);
+  } else {
+    ONESHOT(false, true);
+  }
+#undef ONESHOT
+}
+
+void launch_tiles(const RowsParams& rp, const WindPlan& p, bool chk, hipStream_t stream)
+{
+  if (rp.fc)
+    WIND_LAUNCH(vortdiv_tile_kernel, true, false, true, 8, true);
+  else if (p.tiles.tile_rows == 14)
+    WIND_LAUNCH(vortdiv_tile_kernel, true, true, true, 14);
+  else if (rp.rv && rp.dv)
+    WIND_LAUNCH(vortdiv_tile_kernel, true, true, true, 8);
+  else if (rp.rv)
+    WIND_LAUNCH(vortdiv_tile_kernel, true, false, true, 8);
+  else
+    WIND_LAUNCH(vortdiv_tile_kernel, false, true, true, 8);
+}
+
+void launch_levelwalk(const RowsParams& rp, const WindPlan& p, bool chk, hipStream_t stream)
+{
+  const auto& s = p.levelwalk;
+  if (!(rp.rv && rp.dv)) {
+    if (rp.rv)
+      WIND_LAUNCH(vortdiv_levelwalk_kernel, true, false, true, 12, 1, true);
+    else
+      WIND_LAUNCH(vortdiv_levelwalk_kernel, false, true, true, 12, 1, true);
+    return;
+  }
+#define LEVELWALK(NW_, PF_)                                                         \
+  if (s.waves == NW_ && s.prefetch == PF_) {                                        \
+    if (s.halo_waves)                                                               \
+      WIND_LAUNCH(vortdiv_levelwalk_kernel, true, true, true, NW_, PF_, true);      \
+    else                                                                            \
+      WIND_LAUNCH(vortdiv_levelwalk_kernel, true, true, true, NW_, PF_, false);     \
+  }
+  LEVELWALK(16, 2)
+  LEVELWALK(16, 1)
+  LEVELWALK(12, 2)
+  LEVELWALK(12, 1)
+  LEVELWALK(8, 2)
+  LEVELWALK(8, 1)
+#undef LEVELWALK
+}
+
+void launch_split(const RowsParams& rp, const WindPlan& p, bool jac, bool ragged, bool chk, hipStream_t stream)
+{
+  const auto& s = p.split;
+  // <CHECK, NT, TR, NL, PF, WANT_V, WANT_D, ABSV, FF, RAGGED, JAC>
+#define SPLIT(TR_, NL_, PF_, ...)                                                   \
+  do {                                                                              \
+    if (s.tile_rows == TR_ && s.loaders == NL_ && s.prefetch == PF_)                \
+      WIND_LAUNCH(vortdiv_split_kernel, true, TR_, NL_, PF_, ##__VA_ARGS__);        \
+  } while (0)
+  if (rp.ff) {
+    SPLIT(12, 2, 2, true, true, false, true);
+  } else if (jac) {
+    if (ragged)
+      SPLIT(12, 2, 2, true, false, false, false, true, true);
+    else
+      SPLIT(12, 2, 2, true, false, false, false, false, true);
+  } else if (ragged) {
+    if (rp.fc)
+      SPLIT(12, 2, 2, true, false, true, false, true);
+    else if (rp.rv && rp.dv)
+      SPLIT(12, 2, 2, true, true, false, false, true);
+    else if (rp.rv)
+      SPLIT(12, 2, 2, true, false, false, false, true);
+    else
+      SPLIT(12, 2, 2, false, true, false, false, true);
+  } else if (rp.fc) {
+    SPLIT(12, 2, 1, true, false, true);
+    SPLIT(12, 2, 2, true, false, true);
+  } else if (!rp.dv) {
+    SPLIT(12, 2, 1, true, false, false);
+    SPLIT(12, 2, 2, true, false, false);
+  } else if (!rp.rv) {
+    SPLIT(12, 2, 1, false, true, false);
+    SPLIT(12, 2, 2, false, true, false);
+  } else {
+    SPLIT(6, 2, 3); SPLIT(6, 2, 2); SPLIT(6, 2, 1);
+    SPLIT(8, 2, 3); SPLIT(8, 2, 2); SPLIT(8, 2, 1);
+    SPLIT(12, 4, 2); SPLIT(12, 4, 1);
+    SPLIT(12, 2, 3); SPLIT(12, 2, 2); SPLIT(12, 2, 1);
+    SPLIT(14, 2, 2); SPLIT(14, 2, 1);
+    SPLIT(10, 2, 2); SPLIT(10, 2, 1);
+    SPLIT(10, 4, 3); SPLIT(10, 4, 2); SPLIT(10, 4, 1);
+  }
+#undef SPLIT
+}
+#undef WIND_LAUNCH
 
 inline bool aligned16(const void* p)
 {
@@ -1673,158 +1700,94 @@ size_t padded_level_stride(size_t n)
   return n4;
 }
 
-// Takes the request when the fast path applies (nx % 4 == 0, 16-byte aligned
-// bases and strides); otherwise leaves *handled false and the caller falls
-// back to the one-lane-per-cell kernel.
+// Takes the request when plan_wind() (mifc_vortdiv_plan.h) has a form for it; otherwise leaves *handled false and the
+// caller falls back to the flat kernels.
 hipError_t launch_vortdiv_rows(const StencilParams& prm, hipStream_t stream, bool* handled)
 {
   *handled = false;
+  WindRequest rq{};
   float* rv = nullptr;
   float* dv = nullptr;
   if (prm.op == ST_VORTDIV) {
+    rq.op = WindOp::Vortdiv;
     rv = prm.out0;
     dv = prm.out1;
   } else if (prm.op == ST_RELVORT) {
+    rq.op = WindOp::Relvort;
     rv = prm.out0;
   } else if (prm.op == ST_DIVERGENCE) {
+    rq.op = WindOp::Divergence;
     dv = prm.out0;
   } else if (prm.op == ST_ABSVORT) {
+    rq.op = WindOp::Absvort;
     rv = prm.out0;
-    if (!prm.fcoriolis)
-      return hipSuccess;
   } else if (prm.op == ST_JACOBIAN) {
+    rq.op = WindOp::Jacobian;
     rv = prm.out0;
   } else {
     return hipSuccess;
   }
-  if (!rv && !dv)
+  const bool absv = prm.op == ST_ABSVORT, jac = prm.op == ST_JACOBIAN;
+  rq.nx = prm.nx;
+  rq.ny_global = prm.ny_global;
+  rq.j0 = prm.j0;
+  rq.ny_local = prm.ny_local;
+  rq.nlev = prm.nlev;
+  rq.row_begin = prm.row_begin;
+  rq.row_end = prm.row_end;
+  rq.rv = rv != nullptr;
+  rq.dv = dv != nullptr;
+  rq.ff = prm.out_ff != nullptr;
+  rq.fc = prm.fcoriolis != nullptr;
+  // rows that do not start at 16-byte boundaries: a width that is not a multiple of 4, unaligned fields or level strides
+  rq.ragged = prm.nx % 4 != 0 || !aligned16(prm.f0) || !aligned16(prm.f1) || !aligned16(prm.xmapr) || !aligned16(prm.ymapr) || (rv && !aligned16(rv)) ||
+              (dv && !aligned16(dv)) || prm.in_level_stride % 4 != 0 || prm.out_level_stride % 4 != 0 ||
+              (absv && prm.fcoriolis && !aligned16(prm.fcoriolis));
+  rq.every_level_all_defined = prm.every_level_all_defined != 0;
+  rq.undef_is_nan = prm.undef != prm.undef;
+  rq.has_partials = prm.partials && prm.n_undefined;
+  rq.partials_cap = prm.partials_cap;
+  const WindPlan p = plan_wind(rq, env());
+  if (p.form == WindForm::None)
     return hipSuccess;
-  const int nx = prm.nx;
-  if (nx < 8 || prm.ny_global < 3)
-    return hipSuccess;
-  // Rows that do not start at 16-byte boundaries (a width that is not a multiple of 4, unaligned fields or level strides): only
-  // the split-role kernel has a form for them (RAGGED, round 3), i.e. deep batches of the wind operators; everything else is
-  // left to the flat four-cells-per-lane kernel
-  const bool ragged = nx % 4 != 0 || !aligned16(prm.f0) || !aligned16(prm.f1) || !aligned16(prm.xmapr) || !aligned16(prm.ymapr) || (rv && !aligned16(rv)) ||
-                      (dv && !aligned16(dv)) || prm.in_level_stride % 4 != 0 || prm.out_level_stride % 4 != 0 ||
-                      (prm.op == ST_ABSVORT && prm.fcoriolis && !aligned16(prm.fcoriolis));
-  // (nx % 256 == 1: the column whose value fillEdges copies into column nx-1 belongs to another workgroup)
-  if (ragged && (nx % 256 == 1 || env().has_vortdiv_tune || !env().split_roles || !env().levelwalk || !env().ragged_split || prm.out_ff))
-    return hipSuccess;
-  if (env().force_cell_kernel)
-    return hipSuccess;
+  *handled = true;
+  note_form(p.note);
 
-  // the split-role kernel's tests are ONE compare per value ("ordered and != undef"), which is is_def() only for an
-  // undef that is not NaN: a NaN undef takes the kernels with the generic two-compare test
-  const bool nan_undef_tested = !prm.every_level_all_defined && prm.undef != prm.undef;
-  // the wind speed as a third output exists in the split-role form only (whole fields, fused pair): anything else is left to
-  // the caller, which runs vectorabs as a launch of its own
-  if (prm.out_ff && !(rv && dv && prm.op == ST_VORTDIV && prm.j0 == 0 && prm.ny_local == prm.ny_global && prm.row_end <= prm.row_begin && !nan_undef_tested &&
-                      env().split_roles && env().levelwalk && !env().has_vortdiv_tune && prm.nlev >= kLevelWalkMinLevels))
-    return hipSuccess;
-  Tuning t = current_tuning(nx);
-  while (t.WPB > 1 && t.WPB / 2 >= prm.nlev)
-    t.WPB /= 2; // fewer levels than waves: do not launch waves that only stage map factors
-  if (!env().has_vortdiv_tune) {
-    // A small launch (the reference's single-field call: one level) is latency-bound: shorter
-    // bands put more waves on the chip, and their halo re-reads stay in L2.
-    // One 1440x720 level: 8-row bands 270 waves, 2-row bands 1077; 8 levels (a chunk of the host pipeline) keep 8.
-    const long rows = prm.ny_local, wcols = (nx + 256 * t.V - 1) / (256 * t.V), waves_per_band = (long)prm.nlev * wcols;
-    // (MIFC_LEVELWALK_MIN_UNITS, the tests' switch, sends launches of any size to the level-walking forms)
-    const bool small = env().levelwalk_min_units <= 0 && waves_per_band * ((rows + t.R - 1) / t.R) < 2048;
-    if (small || prm.nlev <= 2) {
-      // ... and the wind operators have forms without any row loop.  Small launches: one 1440x720 level takes
-      // 6.7 us (7.5 us with tests and counts) instead of 7.3 (10.8) with 2-row bands, 12.9 (21.6) with 8-row
-      // bands.  One or two levels of any size: the row-walking workgroup would be one or two waves holding a
-      // 32-KiB map-factor tile (5 waves per CU); a 4000x4000 level straight from HBM runs at 48 % of peak
-      // that way, 66 % one-shot, 69 % as one-shot tiles with the row reuse in LDS
-      // (profiles/r01/other_configs.jsonl, cold numbers).
-      t.K = (small || prm.op == ST_JACOBIAN) ? 1 : 2;
-    }
-    else if (((prm.op != ST_JACOBIAN && prm.op != ST_ABSVORT) || (env().split_roles && !nan_undef_tested)) && prm.nlev >= kLevelWalkMinLevels && env().levelwalk) {
-      // Deep batches: tiles that stay put and walk the levels (map factors once per chunk of levels, a narrow
-      // window of each array open at any time).  12-wave workgroups, 10 computed rows + 2 halo waves, chunks of
-      // about 6 levels (8 in shallower batches), balanced; 3-6 % faster than the row-walking kernel on every device tried
-      // (profiles/r02/experiments/sweep_k3_*.txt).
-      const long tiles = ((rows + 9) / 10) * ((nx + 255) / 256);
-      const int target = prm.nlev >= 48 ? 6 : 8; // levels per chunk; the chunks are then balanced
-      const int nchunks = (prm.nlev + target - 1) / target;
-      if (tiles * nchunks >= (env().levelwalk_min_units > 0 ? env().levelwalk_min_units : kLevelWalkMinUnits)) {
-        t.K = 3;
-        t.RB = 12;
-        t.ZZ = 1;
-        t.D = 0;
-        t.LG = (prm.nlev + nchunks - 1) / nchunks;
-        // The same tiles with split roles -- 2 loader waves bring 14 rows of u and v straight into LDS two levels
-        // ahead, 12 compute waves only read LDS and store (vortdiv_split_kernel).  The fused pair: 1-5 % faster than the
-        // form above on every box, placement and shape tried, 4 % on the tested variant, up to 18 % on shallow batches
-        // (profiles/r02/experiments/sweep_k4_*.txt, ab_split_roles.txt).  Round 3: absvort too (+2 % on the row-walking
-        // kernel it ran before, which has no level-walking form of the first kind); relvort / divergence ALONE measure
-        // the same in both forms (12 B per cell: +-1 %, the sign depends on the box -- profiles/r03/split_role_ops.txt) and
-        // keep the first, MIFC_VORTDIV_TUNE="K=4,..." selects the split-role one.
-        // (single outputs on big tested levels too: that kernel leaves its counts in prm.partials, the first form adds them one by one)
-        const bool big_tested = prm.partials && !prm.every_level_all_defined && tiles >= 2048;
-        if (env().split_roles && !nan_undef_tested && ((rv && dv) || prm.op == ST_ABSVORT || prm.op == ST_JACOBIAN || ragged || big_tested)) {
-          t.K = 4;
-          t.D = 1;
-          t.WPB = 2;
-        }
-      }
-    }
-    while (t.R > 2 && waves_per_band * ((rows + t.R - 1) / t.R) < 2048)
-      t.R /= 2;
-  }
   RowsParams rp;
-  rp.nx = nx;
-  rp.nyg = prm.ny_global - t.PADROWS;
+  rp.nx = prm.nx;
+  rp.nyg = p.nyg;
   rp.j0 = prm.j0;
-  rp.ny_local = prm.ny_local - t.PADROWS;
-  rp.lo = (prm.j0 >= 1) ? 0 : (1 - prm.j0);
-  const int last = rp.nyg - 1 - prm.j0; // local index of the global last row
-  rp.hi = (rp.ny_local < last) ? rp.ny_local : last;
-  if (prm.row_end > prm.row_begin) { // a caller-chosen range of owned rows (halo overlap)
-    rp.lo = rp.lo > prm.row_begin ? rp.lo : prm.row_begin;
-    rp.hi = rp.hi < prm.row_end ? rp.hi : prm.row_end;
-  }
-  if (rp.hi <= rp.lo) {
-    // slab without a single computed row (can only be a 1-row edge slab): not supported here
-    return hipSuccess;
-  }
-  // A row slab carries one halo row before owned row 0 and one after the last
-  // owned row; a whole field has neither.
-  const bool has_north_halo = prm.j0 > 0;
-  const bool has_south_halo = prm.j0 + rp.ny_local < rp.nyg;
-  rp.idx_lo = has_north_halo ? -(long)nx : 0;
-  rp.idx_hi = (long)nx * (rp.ny_local + (has_south_halo ? 1 : 0)) - 1;
-  rp.R = t.R;
-  rp.nbands = (rp.hi - rp.lo + t.R - 1) / t.R;
-  rp.nwc = (nx + 256 * t.V - 1) / (256 * t.V);
+  rp.ny_local = p.ny_local;
+  rp.lo = p.lo;
+  rp.hi = p.hi;
+  rp.R = p.R;
+  rp.nbands = p.nbands;
+  rp.nwc = p.nwc;
   rp.nlev = prm.nlev;
-  rp.wpb = t.WPB;
-  rp.uL = (prm.nlev + t.WPB - 1) / t.WPB;
-  rp.uB = rp.nbands;
-  rp.uW = rp.nwc;
-  const long n_logical = (long)rp.uL * rp.uB * rp.uW;
-  if (n_logical > 0x3fffffffL)
-    return hipSuccess;
-  rp.n_logical = (int)n_logical;
-  rp.per_xcd = (rp.n_logical + 7) / 8;
-  rp.order = t.ORDER;
-  rp.xcd_remap = t.XCD;
-  rp.zigzag = t.ZZ;
-  rp.nt_interior = t.NTI;
-  rp.lgroup = t.LG > 0 ? t.LG : 0;
+  rp.wpb = p.WPB;
+  rp.uL = p.uL;
+  rp.uB = p.uB;
+  rp.uW = p.uW;
+  rp.n_logical = p.n_logical;
+  rp.per_xcd = p.per_xcd;
+  rp.order = p.ORDER;
+  rp.xcd_remap = p.XCD;
+  rp.zigzag = p.ZZ;
+  rp.nt_interior = p.NTI;
+  rp.lgroup = p.lgroup;
 #ifdef MIFC_MEASUREMENT_BUILD
-  rp.exp_nohalo = t.XH;
-  rp.exp_nostore = t.XS;
-  rp.exp_noload = t.XL;
-  rp.exp_store_aux = t.STA;
+  rp.exp_nohalo = p.XH;
+  rp.exp_nostore = p.XS;
+  rp.exp_noload = p.XL;
+  rp.exp_store_aux = p.STA;
 #endif
+  rp.idx_lo = p.idx_lo;
+  rp.idx_hi = p.idx_hi;
   rp.u = prm.f0;
   rp.v = prm.f1;
   rp.xm = prm.xmapr;
   rp.ym = prm.ymapr;
-  rp.fc = (prm.op == ST_ABSVORT) ? prm.fcoriolis : nullptr;
+  rp.fc = absv ? prm.fcoriolis : nullptr;
   rp.rv = rv;
   rp.dv = dv;
   rp.ff = prm.out_ff;
@@ -1834,341 +1797,28 @@ hipError_t launch_vortdiv_rows(const StencilParams& prm, hipStream_t stream, boo
   rp.all_defined = prm.all_defined;
   rp.undef = prm.undef;
   rp.n_undefined = prm.n_undefined;
-  rp.partials = nullptr;
-  // one big level with tests: the one-shot tiles leave their counts in prm.partials and one small launch adds them up (see StencilParams)
-  auto counts_by_partials = [&](long units_per_level, bool level_walking = false) {
-    // (the one-shot tiles index partials[unit of the launch]: level-major only in address order, lgroup == 0)
-    const bool yes = prm.partials && prm.n_undefined && !prm.every_level_all_defined && !prm.out_ff && (level_walking || rp.lgroup == 0) &&
-                     units_per_level >= 2048 && units_per_level * prm.nlev <= prm.partials_cap;
-    rp.partials = yes ? prm.partials : nullptr;
-    return yes;
-  };
-  int grid = rp.per_xcd * 8;
+  rp.partials = p.counts_by_partials ? prm.partials : nullptr;
 
-  if ((prm.out_ff || ragged) && t.K != 4)
-    return hipSuccess; // (see above: only the split-role kernel has the third output / takes rows at any alignment)
-  *handled = true;
-  note_form(t.K == 1 ? "wind_oneshot" : t.K == 2 ? "wind_oneshot_tiles" : t.K == 3 ? "wind_levelwalk"
-            : t.K == 4 ? (ragged ? "wind_split_ragged" : prm.out_ff ? "wind_split_ff" : "wind_split") : "wind_rows");
-  if ((t.K == 1 || t.K == 2) && rp.fc) { // one-shot forms of absvort (relvort + the Coriolis parameter)
-    const bool tiles = t.K == 2;
-    rp.uB = (rp.hi - rp.lo + (tiles ? 7 : 3)) / (tiles ? 8 : 4);
-    rp.uW = (nx + 255) / 256;
-    const long units = (long)prm.nlev * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool chk = !prm.every_level_all_defined;
-      if (tiles) {
-        const bool partials = counts_by_partials((long)rp.uB * rp.uW);
-        if (chk)
-          hipLaunchKernelGGL((vortdiv_tile_kernel<true, true, false, true, 8, true>), dim3(grid), dim3(640), 0, stream, rp);
-        else
-          hipLaunchKernelGGL((vortdiv_tile_kernel<false, true, false, true, 8, true>), dim3(grid), dim3(640), 0, stream, rp);
-        if (partials)
-          (void)launch_count_partials_levels(prm.partials, rp.uB * rp.uW, prm.nlev, prm.n_undefined, stream);
-      } else {
-        if (chk)
-          hipLaunchKernelGGL((vortdiv_oneshot_kernel<true, true, false, true, false, true>), dim3(grid), dim3(256), 0, stream, rp);
-        else
-          hipLaunchKernelGGL((vortdiv_oneshot_kernel<false, true, false, true, false, true>), dim3(grid), dim3(256), 0, stream, rp);
-      }
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
+  const bool chk = !prm.every_level_all_defined;
+  switch (p.form) {
+  case WindForm::Oneshot:
+    launch_oneshot(rp, p, jac, chk, stream);
+    break;
+  case WindForm::OneshotTiles:
+    launch_tiles(rp, p, chk, stream);
+    break;
+  case WindForm::LevelWalk:
+    launch_levelwalk(rp, p, chk, stream);
+    break;
+  case WindForm::Split:
+    launch_split(rp, p, jac, rq.ragged, chk, stream);
+    break;
+  default:
+    launch_rows(rp, p, jac, chk, stream);
+    break;
   }
-  if (t.K == 1 && prm.op == ST_JACOBIAN) { // one-shot form of the Jacobian
-    rp.uB = (rp.hi - rp.lo + 3) / 4;
-    rp.uW = (nx + 255) / 256;
-    const long units = (long)prm.nlev * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      if (prm.every_level_all_defined)
-        hipLaunchKernelGGL((vortdiv_oneshot_kernel<false, true, false, true, true>), dim3(grid), dim3(256), 0, stream, rp);
-      else
-        hipLaunchKernelGGL((vortdiv_oneshot_kernel<true, true, false, true, true>), dim3(grid), dim3(256), 0, stream, rp);
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (t.K == 1 && !rp.fc && prm.op != ST_JACOBIAN) { // one-shot form: units are (level, block of 4 rows, 256-column segment)
-    rp.uB = (rp.hi - rp.lo + 3) / 4;
-    rp.uW = (nx + 255) / 256;
-    const long units = (long)prm.nlev * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool chk = !prm.every_level_all_defined;
-      const int sel = (chk ? 4 : 0) | (rv ? 2 : 0) | (dv ? 1 : 0);
-      switch (sel) {
-#define ONESHOT(C, WV, WD) \
-  if (t.NT) \
-    hipLaunchKernelGGL((vortdiv_oneshot_kernel<C, WV, WD, true>), dim3(grid), dim3(256), 0, stream, rp); \
-  else \
-    hipLaunchKernelGGL((vortdiv_oneshot_kernel<C, WV, WD, false>), dim3(grid), dim3(256), 0, stream, rp); \
-  break
-      case 1:
-        ONESHOT(false, false, true);
-      case 2:
-        ONESHOT(false, true, false);
-      case 3:
-        ONESHOT(false, true, true);
-      case 5:
-        ONESHOT(true, false, true);
-      case 6:
-        ONESHOT(true, true, false);
-      default:
-        ONESHOT(true, true, true);
-#undef ONESHOT
-      }
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (t.K == 4 && nan_undef_tested) { // only a forced tuning gets here: the default selection above never picks K = 4 for these
-    if (rp.fc) { // absvort has no other level-walking form: leave the request to the flat kernel
-      *handled = false;
-      return hipSuccess;
-    }
-    t.K = 3;
-    t.D = 0;
-    t.WPB = 8;
-  }
-  if (t.K == 3 && !rp.fc && prm.op != ST_JACOBIAN && !(rv && dv)) { // level-walking tiles, one output: the default shape only
-    constexpr int NW = 12;
-    rp.uB = (rp.hi - rp.lo + NW - 3) / (NW - 2);
-    rp.uW = (nx + 255) / 256;
-    rp.lgroup = (t.LG > 0 && t.LG < prm.nlev) ? t.LG : prm.nlev;
-    const int nchunks = (prm.nlev + rp.lgroup - 1) / rp.lgroup;
-    const long units = (long)nchunks * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL && (long)nx * (rp.ny_local + 2) < 0x7fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool chk = !prm.every_level_all_defined;
-      if (chk && rv)
-        hipLaunchKernelGGL((vortdiv_levelwalk_kernel<true, true, false, true, NW, 1, true>), dim3(grid), dim3(64 * NW), 0, stream, rp);
-      else if (chk)
-        hipLaunchKernelGGL((vortdiv_levelwalk_kernel<true, false, true, true, NW, 1, true>), dim3(grid), dim3(64 * NW), 0, stream, rp);
-      else if (rv)
-        hipLaunchKernelGGL((vortdiv_levelwalk_kernel<false, true, false, true, NW, 1, true>), dim3(grid), dim3(64 * NW), 0, stream, rp);
-      else
-        hipLaunchKernelGGL((vortdiv_levelwalk_kernel<false, false, true, true, NW, 1, true>), dim3(grid), dim3(64 * NW), 0, stream, rp);
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (t.K == 3 && !rp.fc && prm.op != ST_JACOBIAN && rv && dv) { // level-walking tiles: units are (level chunk, row block, 256-column segment)
-    const int NWsel = (t.RB == 16 || t.RB == 12 || t.RB == 8) ? t.RB : 16; // RB doubles as the waves per workgroup here
-    const bool halo_waves = t.ZZ != 0;                                     // ZZ doubles as "the halo rows have waves of their own"
-    const int tile_rows = halo_waves ? NWsel - 2 : NWsel;
-    rp.uB = (rp.hi - rp.lo + tile_rows - 1) / tile_rows;
-    rp.uW = (nx + 255) / 256;
-    rp.lgroup = (t.LG > 0 && t.LG < prm.nlev) ? t.LG : prm.nlev; // levels per workgroup
-    const int nchunks = (prm.nlev + rp.lgroup - 1) / rp.lgroup;
-    const long units = (long)nchunks * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL && (long)nx * (rp.ny_local + 2) < 0x7fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool chk = !prm.every_level_all_defined;
-      const int pf = t.D >= 1 ? 2 : 1; // D doubles as the prefetch depth selector: D=0 -> one level ahead, D=1 (default) -> two
-#define LEVELWALK(NW_, PF_)                                                                                                                          \
-  if (chk && halo_waves)                                                                                                                             \
-    hipLaunchKernelGGL((vortdiv_levelwalk_kernel<true, true, true, true, NW_, PF_, true>), dim3(grid), dim3(64 * NW_), 0, stream, rp);               \
-  else if (chk)                                                                                                                                      \
-    hipLaunchKernelGGL((vortdiv_levelwalk_kernel<true, true, true, true, NW_, PF_, false>), dim3(grid), dim3(64 * NW_), 0, stream, rp);              \
-  else if (halo_waves)                                                                                                                               \
-    hipLaunchKernelGGL((vortdiv_levelwalk_kernel<false, true, true, true, NW_, PF_, true>), dim3(grid), dim3(64 * NW_), 0, stream, rp);              \
-  else                                                                                                                                               \
-    hipLaunchKernelGGL((vortdiv_levelwalk_kernel<false, true, true, true, NW_, PF_, false>), dim3(grid), dim3(64 * NW_), 0, stream, rp)
-      if (NWsel == 16 && pf == 2) {
-        LEVELWALK(16, 2);
-      } else if (NWsel == 16) {
-        LEVELWALK(16, 1);
-      } else if (NWsel == 12 && pf == 2) {
-        LEVELWALK(12, 2);
-      } else if (NWsel == 12) {
-        LEVELWALK(12, 1);
-      } else if (pf == 2) {
-        LEVELWALK(8, 2);
-      } else {
-        LEVELWALK(8, 1);
-      }
-#undef LEVELWALK
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (t.K == 4 && prm.op == ST_JACOBIAN && env().has_vortdiv_tune) { // a forced tuning: the Jacobian has the default shape only
-    *handled = false;
-    return hipSuccess;
-  }
-  if (t.K == 4) { // split-role level-walking tiles (loader waves / compute waves)
-    const bool single = !(rv && dv) || rp.fc; // one output: the default shape only (and its one-level-ahead sibling)
-    const int tile_rows = (single || ragged || prm.out_ff) ? 12 : ((t.RB == 6 || t.RB == 8 || t.RB == 12 || t.RB == 14) ? t.RB : 10);
-    const int nchunks_lg = (t.LG > 0 && t.LG < prm.nlev) ? t.LG : prm.nlev; // levels per workgroup
-    const int nchunks = (prm.nlev + nchunks_lg - 1) / nchunks_lg;
-    const long units = (long)nchunks * ((rp.hi - rp.lo + tile_rows - 1) / tile_rows) * ((nx + 255) / 256);
-    if (units > 0x3fffffffL || (long)nx * (rp.ny_local + 2) >= 0x7fffffffL) { // 32-bit offsets inside a level: not this kernel's case
-      *handled = false;
-      return hipSuccess;
-    }
-    rp.uB = (rp.hi - rp.lo + tile_rows - 1) / tile_rows;
-    rp.uW = (nx + 255) / 256;
-    rp.lgroup = nchunks_lg;
-    rp.n_logical = (int)units;
-    rp.per_xcd = (rp.n_logical + 7) / 8;
-    grid = rp.per_xcd * 8;
-    const bool chk = !prm.every_level_all_defined;
-    const bool partials = counts_by_partials((long)rp.uB * rp.uW, true); // big levels: counts by plain stores + one small launch
-    auto finish = [&]() {
-      if (partials)
-        (void)launch_count_partials_levels(prm.partials, rp.uB * rp.uW, prm.nlev, prm.n_undefined, stream);
-      return hipGetLastError();
-    };
-    const int pf = t.D >= 2 ? 3 : (t.D == 1 ? 2 : 1); // D selects how many levels the loaders run ahead
-    const int nl = (t.WPB == 2 || t.WPB == 4) ? t.WPB : (tile_rows == 10 ? 4 : 2); // WPB doubles as the number of loader waves
-#define SPLIT_AS(TR_, NL_, PF_, ...)                                                                                                       \
-  if (chk)                                                                                                                                 \
-    hipLaunchKernelGGL((vortdiv_split_kernel<true, true, TR_, NL_, PF_, ##__VA_ARGS__>), dim3(grid), dim3(64 * (TR_ + NL_)), 0, stream, rp); \
-  else                                                                                                                                     \
-    hipLaunchKernelGGL((vortdiv_split_kernel<false, true, TR_, NL_, PF_, ##__VA_ARGS__>), dim3(grid), dim3(64 * (TR_ + NL_)), 0, stream, rp)
-    if (prm.out_ff) { // the fused pair plus the wind speed: the default shape
-      SPLIT_AS(12, 2, 2, true, true, false, true);
-      return finish();
-    }
-    if (prm.op == ST_JACOBIAN) { // the default shape, rows at any alignment or not
-      if (ragged) {
-        SPLIT_AS(12, 2, 2, true, false, false, false, true, true);
-      } else {
-        SPLIT_AS(12, 2, 2, true, false, false, false, false, true);
-      }
-      return finish();
-    }
-    if (ragged) { // rows at any alignment: the default shape
-      if (rp.fc) {
-        SPLIT_AS(12, 2, 2, true, false, true, false, true);
-      } else if (rv && dv) {
-        SPLIT_AS(12, 2, 2, true, true, false, false, true);
-      } else if (rv) {
-        SPLIT_AS(12, 2, 2, true, false, false, false, true);
-      } else {
-        SPLIT_AS(12, 2, 2, false, true, false, false, true);
-      }
-      return finish();
-    }
-    if (single) {
-      const bool pf1 = pf == 1;
-      if (rp.fc) {
-        if (pf1) { SPLIT_AS(12, 2, 1, true, false, true); } else { SPLIT_AS(12, 2, 2, true, false, true); }
-      } else if (rv) {
-        if (pf1) { SPLIT_AS(12, 2, 1, true, false, false); } else { SPLIT_AS(12, 2, 2, true, false, false); }
-      } else {
-        if (pf1) { SPLIT_AS(12, 2, 1, false, true, false); } else { SPLIT_AS(12, 2, 2, false, true, false); }
-      }
-      return finish();
-    }
-#define SPLIT(TR_, NL_, PF_) SPLIT_AS(TR_, NL_, PF_)
-    if (tile_rows == 6) {
-      if (pf == 3) { SPLIT(6, 2, 3); } else if (pf == 2) { SPLIT(6, 2, 2); } else { SPLIT(6, 2, 1); }
-    } else if (tile_rows == 8) {
-      if (pf == 3) { SPLIT(8, 2, 3); } else if (pf == 2) { SPLIT(8, 2, 2); } else { SPLIT(8, 2, 1); }
-    } else if (tile_rows == 12 && nl == 4) {
-      if (pf >= 2) { SPLIT(12, 4, 2); } else { SPLIT(12, 4, 1); }
-    } else if (tile_rows == 12) {
-      if (pf == 3) { SPLIT(12, 2, 3); } else if (pf == 2) { SPLIT(12, 2, 2); } else { SPLIT(12, 2, 1); }
-    } else if (tile_rows == 14) { // 16 waves: two loaders at most
-      if (pf >= 2) { SPLIT(14, 2, 2); } else { SPLIT(14, 2, 1); }
-    } else if (nl == 2) {
-      if (pf >= 2) { SPLIT(10, 2, 2); } else { SPLIT(10, 2, 1); }
-    } else {
-      if (pf == 3) { SPLIT(10, 4, 3); } else if (pf == 2) { SPLIT(10, 4, 2); } else { SPLIT(10, 4, 1); }
-    }
-#undef SPLIT
-#undef SPLIT_AS
-    return finish();
-  }
-  if (t.K == 2 && !rp.fc && prm.op != ST_JACOBIAN && t.RB == 14 && rv && dv) { // one-shot tiles of 14 rows (16-wave workgroups)
-    constexpr int RB = 14;
-    rp.uB = (rp.hi - rp.lo + RB - 1) / RB;
-    rp.uW = (nx + 255) / 256;
-    const long units = (long)prm.nlev * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool partials = counts_by_partials((long)rp.uB * rp.uW);
-      if (prm.every_level_all_defined)
-        hipLaunchKernelGGL((vortdiv_tile_kernel<false, true, true, true, RB>), dim3(grid), dim3(64 * (RB + 2)), 0, stream, rp);
-      else
-        hipLaunchKernelGGL((vortdiv_tile_kernel<true, true, true, true, RB>), dim3(grid), dim3(64 * (RB + 2)), 0, stream, rp);
-      if (partials)
-        (void)launch_count_partials_levels(prm.partials, rp.uB * rp.uW, prm.nlev, prm.n_undefined, stream);
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (t.K == 2 && !rp.fc && prm.op != ST_JACOBIAN) { // one-shot tiles: units are (level, block of 8 rows, 256-column segment)
-    constexpr int RB = 8;
-    rp.uB = (rp.hi - rp.lo + RB - 1) / RB;
-    rp.uW = (nx + 255) / 256;
-    const long units = (long)prm.nlev * rp.uB * rp.uW;
-    if (units <= 0x3fffffffL) {
-      rp.n_logical = (int)units;
-      rp.per_xcd = (rp.n_logical + 7) / 8;
-      grid = rp.per_xcd * 8;
-      const bool chk = !prm.every_level_all_defined;
-      const int sel = (chk ? 4 : 0) | (rv ? 2 : 0) | (dv ? 1 : 0);
-      const bool partials = counts_by_partials((long)rp.uB * rp.uW);
-      switch (sel) {
-#define TILE(C, WV, WD) \
-  hipLaunchKernelGGL((vortdiv_tile_kernel<C, WV, WD, true, RB>), dim3(grid), dim3(64 * (RB + 2)), 0, stream, rp); \
-  break
-      case 1:
-        TILE(false, false, true);
-      case 2:
-        TILE(false, true, false);
-      case 3:
-        TILE(false, true, true);
-      case 5:
-        TILE(true, false, true);
-      case 6:
-        TILE(true, true, false);
-      default:
-        TILE(true, true, true);
-#undef TILE
-      }
-      if (partials)
-        (void)launch_count_partials_levels(prm.partials, rp.uB * rp.uW, prm.nlev, prm.n_undefined, stream);
-      return hipGetLastError();
-    }
-    *handled = false; // a level or a launch beyond the 32-bit index range of these forms: rp was changed for them, so not the row kernel below either
-    return hipSuccess;
-  }
-  if (prm.op == ST_JACOBIAN) {
-    if (t.V == 3)
-      t.V = 2;
-    if (prm.every_level_all_defined)
-      launch_jacobian<false>(rp, t, grid, stream);
-    else
-      launch_jacobian<true>(rp, t, grid, stream);
-    return hipGetLastError();
-  }
-  if (prm.every_level_all_defined)
-    launch_outputs<false>(rp, t, grid, stream);
-  else
-    launch_outputs<true>(rp, t, grid, stream);
+  if (p.counts_by_partials) // one small launch adds the workgroups' counts up (see StencilParams)
+    (void)launch_count_partials_levels(prm.partials, p.uB * p.uW, prm.nlev, prm.n_undefined, stream);
   return hipGetLastError();
 }
 
