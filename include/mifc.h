@@ -297,6 +297,38 @@ int mifc_extremeValue(mifc_ctx* ctx, int compute, int nx, int ny, const float* c
 int mifc_probability(mifc_ctx* ctx, int compute, int nx, int ny, const float* const* fields, const int* fdefined_in, int nfields,
                      const float* limits, int nlimits, float* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- the ensemble reductions over a level batch, several in one pass over the members -----------------------
+ * The five functions above for nmem members of [nlev][ny][nx] each and a list of products: for every level l and product
+ * k, products[k].out[l] and products[k].fdefined[l] are bit for bit what the single-field function of products[k].stat
+ * returns for level l of the members, its quirks included (members reduced in index order; sumFields stops at the first
+ * undefined member; Welford in float; sqrt in double; probability tests != undef only and leaves out the members flagged
+ * NONE_DEFINED; the index variants of extremeValue store (float)j).  Every member is read once per call, whatever the
+ * number of products.
+ *   `fields` is a HOST array of nmem pointers, each to [nlev][ny][nx]; `fdefined_in` a HOST int[nmem * nlev], member-major
+ *   (j * nlev + l), NULL = all SOME_DEFINED: the reference's fDefinedIn[j] of meanValue, stddevValue and probability.
+ *   `products` is a HOST array.  sumFields and extremeValue take ONE in/out flag in the reference: here that is
+ *   products[k].fdefined[l], on input the state of that level's members (ALL_DEFINED switches the per-cell tests off), on
+ *   output the result flag.  For the other statistics products[k].fdefined[l] is output only.
+ * One list holds at most one SUM, one MEAN, one STDDEV, one EXTREME per compute 1..4 and eight PROBABILITY products.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nproducts < 1 or a list past
+ * these limits; an unknown stat; EXTREME compute outside 1..4; PROBABILITY compute outside 1..6, nlimits outside 1..2, or
+ * compute 3 / 6 with one limit (the reference returns false); EXTREME with nmem == 0 (likewise); nlev < 1, or a negative
+ * nx, ny or nmem; a null pointer; an output that overlaps another output or a member; a call made while a mifc_graph
+ * capture is open.  nmem == 0 with the other statistics gives what the reference gives for an empty vector.
+ * memkind works as everywhere else; host memory works at any size: the call stages a bounded chunk of levels (or of one
+ * level's cells) at a time, MIFC_ENSEMBLE_CHUNK_MIB of device memory (default 256).  DESIGN.md 4.14. */
+enum { MIFC_ENS_SUM = 0, MIFC_ENS_MEAN = 1, MIFC_ENS_STDDEV = 2, MIFC_ENS_EXTREME = 3, MIFC_ENS_PROBABILITY = 4 };
+typedef struct mifc_ens_product {
+  int stat;        /* MIFC_ENS_* */
+  int compute;     /* EXTREME 1..4, PROBABILITY 1..6 (the reference's numbering); ignored otherwise */
+  float limits[2]; /* PROBABILITY */
+  int nlimits;     /* PROBABILITY: 1 or 2 */
+  float* out;      /* [nlev][ny][nx], host or device per memkind */
+  int* fdefined;   /* HOST int[nlev]; see above */
+} mifc_ens_product;
+int mifc_ensemble_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nmem,
+                         const mifc_ens_product* products, int nproducts, float undef, int memkind);
+
 /* ---- EXTENSION: percentiles across ensemble members ---------------------------------------------------------
  * Not a miutil::fieldcalc function; the reference's rule for choosing a percentile is neighbourFunctions compute 4
  * (FieldCalculations.cc:2955-3061).  Inputs are nmem members.  Each member is a [nlev][ny][nx] float field, with one

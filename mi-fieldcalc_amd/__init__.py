@@ -23,7 +23,75 @@ ALL_DEFINED, NONE_DEFINED, SOME_DEFINED = 0, 1, 2  # miutil::ValuesDefined, Fiel
 UNDEF = np.float32(1.0e35)  # miutil::UNDEF, FieldDefined.cc:34
 MEM_HOST, MEM_DEVICE = 0, 1
 
-__all__ = ["Context", "SlabPlan", "Graph", "PreparedCalls", "ALL_DEFINED", "NONE_DEFINED", "SOME_DEFINED", "UNDEF", "classify"]
+__all__ = ["Context", "SlabPlan", "Graph", "PreparedCalls", "ALL_DEFINED", "NONE_DEFINED", "SOME_DEFINED", "UNDEF", "classify",
+           "ensemble_products"]
+
+# mifc_ens_product.stat (include/mifc.h), and the names Context.ensembleStatistics takes for them
+ENS_SUM, ENS_MEAN, ENS_STDDEV, ENS_EXTREME, ENS_PROBABILITY = 0, 1, 2, 3, 4
+_ENS_EXTREMES = {"max": 1, "min": 2, "argmax": 3, "argmin": 4}
+_ENS_MAX_PROBABILITIES = 8
+
+
+def ensemble_products(products):
+    """The product specs of Context.ensembleStatistics as a list of (stat, compute, limits, flag_in) tuples, validated
+    the way mifc_ensemble_levels validates its list (a bad list raises ValueError here, before anything is allocated).
+    A spec is "mean", "stddev", "sum", "max", "min", "argmax", "argmin" (a bare name or a 1-tuple), ("sum", flag_in),
+    ("max", flag_in) ... with flag_in one ValuesDefined flag or one per level (default SOME_DEFINED), ("extreme", compute,
+    flag_in), or ("probability", compute, limits) with the reference's compute 1..6 and one or two limits.  flag_in is
+    None where the statistic has no input flag of its own."""
+    out, seen, nprob = [], set(), 0
+    for spec in products:
+        try:
+            spec = (spec,) if isinstance(spec, str) else tuple(spec)
+        except TypeError:
+            spec = ()
+        if not spec or not isinstance(spec[0], str):
+            raise ValueError("a product is a name or a tuple that starts with one: %r" % (spec,))
+        name, rest = spec[0].lower(), spec[1:]
+        if name in ("mean", "stddev"):
+            if rest:
+                raise ValueError("%r takes no arguments (the member flags are fdefined_in)" % name)
+            item = (ENS_MEAN if name == "mean" else ENS_STDDEV, 0, (), None)
+            key = name
+        elif name == "sum" or name in _ENS_EXTREMES or name == "extreme":
+            if name == "extreme":
+                if not rest:
+                    raise ValueError('("extreme", compute[, flag_in])')
+                compute, rest = int(rest[0]), rest[1:]
+                if compute not in (1, 2, 3, 4):
+                    raise ValueError("extreme: compute %d outside 1..4" % compute)
+            else:
+                compute = _ENS_EXTREMES.get(name, 0)
+            if len(rest) > 1:
+                raise ValueError("%r takes one argument, the input flag" % name)
+            item = (ENS_SUM if name == "sum" else ENS_EXTREME, compute, (), rest[0] if rest else SOME_DEFINED)
+            key = "sum" if name == "sum" else ("extreme", compute)
+        elif name == "probability":
+            if len(rest) != 2:
+                raise ValueError('("probability", compute, limits)')
+            compute = int(rest[0])
+            limits = tuple(float(x) for x in np.atleast_1d(np.asarray(rest[1], dtype=np.float32)))
+            if compute not in (1, 2, 3, 4, 5, 6):
+                raise ValueError("probability: compute %d outside 1..6" % compute)
+            if len(limits) not in (1, 2):
+                raise ValueError("probability: one or two limits, not %d" % len(limits))
+            if compute in (3, 6) and len(limits) == 1:
+                raise ValueError("probability: between (compute %d) needs two limits" % compute)
+            nprob += 1
+            if nprob > _ENS_MAX_PROBABILITIES:
+                raise ValueError("more than %d probability products" % _ENS_MAX_PROBABILITIES)
+            item = (ENS_PROBABILITY, compute, limits, None)
+            key = None
+        else:
+            raise ValueError("unknown statistic %r" % (spec[0],))
+        if key is not None:
+            if key in seen:
+                raise ValueError("%r is in the list twice" % (spec[0],))
+            seen.add(key)
+        out.append(item)
+    if not out:
+        raise ValueError("no products")
+    return out
 
 
 def classify(n_undefined, n):
@@ -560,6 +628,62 @@ class Context:
                                                       float(undef), mk]):
             raise RuntimeError("mifc_ensembleQuantiles: " + self.last_error())
         return (out if _is_torch(out) else oa.keep), (int(fd[0]) if len(shape) == 2 else fd)
+
+    def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
+        """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability
+        over the same members in one pass, each bit for bit what its single-field function returns per level.
+        fields: as ensembleQuantiles takes them.  products: see ensemble_products().  fdefined_in: member flags, (nmem,)
+        or (nmem, nlev); None: SOME_DEFINED.  out: one array or tensor of shape (len(products),) + the member shape, or a
+        sequence of one per product.  Returns a list of (array, flags) in product order: flags an int for 2-D members,
+        an int32 array of nlev flags otherwise.  A refused call raises RuntimeError with the reason."""
+        specs = ensemble_products(products)
+        members = [fields[j] for j in range(fields.shape[0])] if isinstance(fields, np.ndarray) or _is_torch(fields) else list(fields)
+        fa = [_Arg(m) for m in members]
+        if out is not None and (isinstance(out, np.ndarray) or _is_torch(out)):
+            out = [out[k] for k in range(out.shape[0])]
+        if out is not None and len(out) != len(specs):
+            raise ValueError("out must hold one array per product")
+        if fa:
+            shape = tuple(fa[0].shape)
+        elif out is not None:
+            shape = tuple(_Arg(out[0], output=True).shape)
+        else:
+            raise ValueError("no member fields and no output to take the shape from")
+        if len(shape) not in (2, 3):
+            raise ValueError("members must be (ny, nx) or (nlev, ny, nx) fields")
+        if not _same_shape(fa, shape):
+            raise ValueError("every member must have the shape %s" % (shape,))
+        nlev = shape[0] if len(shape) == 3 else 1
+        ny, nx = shape[-2], shape[-1]
+        if out is None:
+            out = [_empty_like(members[0], shape) for _ in specs]
+        oa = [_Arg(o, output=True) for o in out]
+        if not _same_shape(oa, shape):
+            raise ValueError("every output must have the shape %s" % (shape,))
+        mk = _memkind(fa + oa, self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * max(len(fa), 1))(*[a.addr for a in fa])
+        flags = None
+        if fdefined_in is not None:
+            f = np.asarray(fdefined_in, dtype=np.int32)
+            if f.ndim == 1:
+                f = np.repeat(f[:, None], nlev, axis=1)
+            flags = np.ascontiguousarray(f.reshape(len(fa), nlev), dtype=np.int32)
+        fds = []
+        prods = (_capi.EnsProduct * len(specs))()
+        for k, (stat, compute, limits, flag_in) in enumerate(specs):
+            fd = np.full(nlev, SOME_DEFINED, np.int32)
+            if flag_in is not None:
+                fd[:] = np.asarray(flag_in, dtype=np.int32).reshape(-1) if np.ndim(flag_in) else int(flag_in)
+            fds.append(fd)
+            prods[k].stat, prods[k].compute, prods[k].nlimits = stat, compute, len(limits)
+            for i, v in enumerate(limits):
+                prods[k].limits[i] = v
+            prods[k].out, prods[k].fdefined = oa[k].addr, fd.ctypes.data
+        if not self._call("mifc_ensemble_levels", [nx, ny, nlev, ctypes.addressof(table), flags, len(fa), ctypes.addressof(prods), len(specs),
+                                                    float(undef), mk]):
+            raise RuntimeError("mifc_ensemble_levels: " + self.last_error())
+        return [((o if _is_torch(o) else a.keep), (int(fd[0]) if len(shape) == 2 else fd)) for o, a, fd in zip(out, oa, fds)]
 
     # ------------------------------------------------------ neighbourhood statistics
     # out=None allocates an output pre-filled with `undef`: the reference leaves some cells unwritten (neighbourFunctions:

@@ -124,6 +124,8 @@ SIGNATURES = {
     "mifc_probability": ("i", ["ctx", "i", "i", "i", "p", "p", "i", "p", "i", "p", "pi", "f", "i"]),
     # EXTENSION: percentiles across members (fields, fres: host tables of pointers; percentiles: host float array)
     "mifc_ensembleQuantiles": ("i", ["ctx", "i", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "f", "i"]),
+    # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
+    "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)
     "mifc_neighbourProbFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_neighbourFunctions": ("i", ["ctx", "i", "i", "p", "p", "i", "i", "p", "pi", "f", "i"]),
@@ -183,6 +185,19 @@ SIGNATURES = {
     "mifc_slab_plan_begin": ("i", ["p"]),
     "mifc_slab_plan_finish": ("i", ["p"]),
 }
+
+
+class EnsProduct(ctypes.Structure):
+    """mifc_ens_product of include/mifc.h."""
+
+    _fields_ = [
+        ("stat", ctypes.c_int),
+        ("compute", ctypes.c_int),
+        ("limits", ctypes.c_float * 2),
+        ("nlimits", ctypes.c_int),
+        ("out", ctypes.c_void_p),
+        ("fdefined", ctypes.c_void_p),
+    ]
 
 
 # entry points of the measurement build only (include/mifc_measure.h): bound when the loaded library has them, i.e. when

@@ -94,13 +94,7 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
   if (host) {
     // bounded staging: whole levels while they fit, else a range of cells of one level
     const size_t budget = (size_t)(mifc::env().quantile_chunk_mib > 0 ? mifc::env().quantile_chunk_mib : 256) << 20;
-    const size_t per_cell = (size_t)(nmem + nq) * sizeof(float);
-    if (cells * per_cell <= budget) {
-      lev_chunk = std::min((size_t)nlev, budget / (cells * per_cell));
-    } else {
-      lev_chunk = 1;
-      cell_chunk = std::max((size_t)1, budget / per_cell);
-    }
+    plan_level_chunks(budget, cells, (size_t)(nmem + nq) * sizeof(float), (size_t)nlev, &lev_chunk, &cell_chunk);
     S = align_up(lev_chunk * cell_chunk, 64);
     const float* d_mem = nmem > 0 ? static_cast<const float*>(st.scratch((size_t)nmem * S * sizeof(float))) : nullptr;
     float* d_out = static_cast<float*>(st.scratch((size_t)nq * S * sizeof(float)));

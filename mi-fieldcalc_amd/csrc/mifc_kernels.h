@@ -243,6 +243,59 @@ inline int quantile_blocks(int n)
 }
 hipError_t launch_quantiles(const QuantileParams& prm, hipStream_t stream);
 
+// ------------------------------------ several ensemble reductions in one pass over the members (mifc_ensemble_levels.hip)
+// One launch covers `nlev` levels of `n` cells each, laid out as for launch_quantiles.  The products of a call sit in
+// fixed slots: 0 sumFields, 1 meanValue, 2 stddevValue, 2 + c extremeValue compute c (1..4), 7..14 probability; slot k is
+// live when bit k of `live` is set, its result goes to out[k] and its undefined count to n_undefined[k * call_nlev + level].
+// The product parameters are of fixed size and always travel in the kernel arguments; what grows with the call (member
+// pointers, per-level member bits, per-level defined-member counts and input flags) does so up to 64 members and 64 levels
+// and sits in the device table beyond.
+const int ENSLV_SLOTS = 15, ENSLV_EXT0 = 2, ENSLV_PROB0 = 7, ENSLV_NPROB = 8, ENSLV_KARG_MEM = 64, ENSLV_KARG_LEVELS = 64;
+struct EnsLevelsTable // device memory, used when inline_args == 0
+{
+  const float* const* mem;     // [nmem]
+  const u64* all_bits;         // [level][words]: member j's flag is ALL_DEFINED at that level
+  const u64* none_bits;        // [level][words]: member j's flag is NONE_DEFINED (probability leaves it out)
+  const int* ndef;             // [level]: members not flagged NONE_DEFINED (probability's nfields_defined)
+  const unsigned char* in_all; // [level]: bit 0 sumFields', bit c extremeValue compute c's input flag is ALL_DEFINED
+};
+struct EnsLevelsParams
+{
+  int nlev;      // levels of this launch
+  int lev0;      // the call's level of the launch's level 0 (bits, counters)
+  int call_nlev; // levels of the whole call: the distance between the counters of two slots
+  int n;         // cells per level
+  long stride;   // floats between consecutive levels of every member and output of the launch
+  int nmem;
+  int words;     // (nmem + 63) / 64
+  int vector_ok; // every member and output is 16-byte aligned, and so is every level inside them
+  unsigned int live;
+  float undef;
+  float* out[ENSLV_SLOTS];
+  // probability slot i (:2821-2825) in bit i; percent: compute < 4
+  unsigned int check_above, check_below, percent;
+  float value_above[ENSLV_NPROB], value_below[ENSLV_NPROB];
+  u64* n_undefined;       // [ENSLV_SLOTS][call_nlev], zeroed by the caller
+  unsigned int* partials; // [slot][launch level][workgroup] counts of big launches (see EwiseParams), or null
+  int partials_cap;
+  int inline_args;
+  EnsLevelsTable tab;
+  const float* mem_inline[ENSLV_KARG_MEM];
+  u64 all_inline[ENSLV_KARG_LEVELS], none_inline[ENSLV_KARG_LEVELS]; // nmem <= 64: one word per level
+  unsigned char ndef_inline[ENSLV_KARG_LEVELS], in_all_inline[ENSLV_KARG_LEVELS];
+};
+// workgroups per level of a launch over n cells (the host sizes the partial-count buffer with it)
+inline int ensemble_levels_blocks(int n, bool vec4)
+{
+  const long lanes = vec4 ? (long)(n >> 2) : (long)n, want = (lanes + 255) / 256;
+  return (int)(want < 1 ? 1 : (want > 65535 ? 65535 : want));
+}
+inline bool ensemble_levels_vec4(const EnsLevelsParams& P)
+{
+  return P.vector_ok && P.n >= 4 && (P.n & 3) == 0;
+}
+hipError_t launch_ensemble_levels(const EnsLevelsParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
