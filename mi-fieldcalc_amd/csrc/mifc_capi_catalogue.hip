@@ -124,10 +124,15 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
       float* d = members + (size_t)j * stride;
       MIFC_HIP(c, hipMemcpyAsync(d, fields[j], n * sizeof(float), hipMemcpyHostToDevice, c->stream));
       table[(size_t)j] = d;
+      if (fields[j] == out) // reduced in place: every member that is the output shares one staged copy, named to the kernel
+        table[(size_t)j] = P.out_member ? P.out_member : (P.out_member = d);
     }
   } else {
-    for (int j = 0; j < nfields; ++j)
+    for (int j = 0; j < nfields; ++j) {
       table[(size_t)j] = fields[j];
+      if (fields[j] == out)
+        P.out_member = out;
+    }
   }
   P.out = st.out(out, n, may_keep);
   const size_t table_bytes = align_up((size_t)nfields * sizeof(float*), 16);

@@ -131,6 +131,13 @@ __device__ __forceinline__ unsigned char ens_flag(const EnsembleParams& P, int j
   return P.member_flags ? P.member_flags[j] : (unsigned char)(P.all_defined ? 0 : 2);
 }
 
+// member j is the array the caller's output overwrites: what the reference reads there is fres[i], its running result
+template <int OP>
+__device__ __forceinline__ bool ens_aliased(const EnsembleParams& P, int j)
+{
+  return OP != ENS_STDDEV && P.out_member != nullptr && ens_field(P, j) == P.out_member;
+}
+
 template <int OP, bool VEC4>
 __global__ __launch_bounds__(256) void ensemble_kernel(const EnsembleParams P)
 {
@@ -162,10 +169,11 @@ __global__ __launch_bounds__(256) void ensemble_kernel(const EnsembleParams P)
             const unsigned char fl = ens_flag(P, j);
             const bool m_all = fl == 0, m_none = fl == 1;
             const float f[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+            const bool own = ens_aliased<OP>(P, j);
 #pragma unroll
             for (int c = 0; c < 4; ++c)
               if (live[c])
-                live[c] = ens_member<OP>(P, a[c], j, f[c], m_all, m_none);
+                live[c] = ens_member<OP>(P, a[c], j, own ? a[c].r : f[c], m_all, m_none);
           }
         }
       }
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(256) void ensemble_kernel(const EnsembleParams P)
       bool live = true;
       for (int j = 0; j < P.nfields && live; ++j) {
         const unsigned char fl = ens_flag(P, j);
-        live = ens_member<OP>(P, a, j, ens_field(P, j)[i], fl == 0, fl == 1);
+        live = ens_member<OP>(P, a, j, ens_aliased<OP>(P, j) ? a.r : ens_field(P, j)[i], fl == 0, fl == 1);
       }
       if (keep_all)
         continue;

@@ -188,6 +188,10 @@ struct EnsembleParams
   float undef;
   const float* const* fields; // device table of nfields device pointers
   float* out;
+  // The caller's output IS a member's array (fres == fields[j], callers reduce in place): the device copy of that
+  // member, else null.  The reference accumulates in fres[i] (:2681, :2707, :2776, :2838), so it reads its own running
+  // result where that member was; the kernel does the same (ens_aliased).  stddevValue writes fres[i] last and is not affected.
+  const float* out_member;
   u64* n_undefined;
   // up to 64 members (an ensemble: 51) travel in the kernel arguments: no table upload before the launch
   int n_inline;         // != 0: use the arrays below instead of `fields` / `member_flags`

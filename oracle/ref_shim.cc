@@ -8,6 +8,12 @@
  * It exists so that Python (ctypes) can call miutil::fieldcalc::* without
  * having to fabricate std::string / enum references.
  *
+ * The same file, compiled with -DMIFC_SHIM_KIND_NAME="dropin" against the
+ * product's source-compatible headers and linked against libmi-fieldcalc.so
+ * instead (oracle/Makefile, target libmifc_dropin.so), gives the same flat
+ * entry points over the product's C++ API: the tests then drive the layer a
+ * caller of the reference links, operator by operator.
+ *
  * Only tests/, tests/golden/make_golden.py, __graft_entry__.smoke() and
  * bench.py's cpu_baseline leg may load the resulting library.
  */
@@ -18,6 +24,7 @@
 #include <mi_fieldcalc/mi_fieldcalc_version.h>
 
 #include <string>
+#include <vector>
 
 namespace fc = miutil::fieldcalc;
 
@@ -183,11 +190,29 @@ int mifcref_plevelqvector(int nx, int ny, const float* z, const float* t, const 
   return fc::plevelqvector(nx, ny, z, t, xmapr, ymapr, fcoriolis, p, compute, qcomp, f.v, undef);
 }
 
+#ifdef MIFC_SHIM_KIND_NAME
+// Only the drop-in build names its kind, and only the product's header declares these: last_error(), and the
+// reference function that is declared but not built on the GPU (the one call that sets a "not built" message).
+const char* mifcref_last_error(void)
+{
+  return fc::last_error();
+}
+
+int mifcref_neighbourFunctions(int nx, int ny, const float* field, const float* constants, int nconstants, int compute, float* fres, int* fdefined,
+                               float undef)
+{
+  Flag f(fdefined);
+  return fc::neighbourFunctions(nx, ny, field, std::vector<float>(constants, constants + nconstants), compute, fres, f.v, undef);
+}
+#else
+#define MIFC_SHIM_KIND_NAME "reference"
+#endif
+
 #define MIFC_STR0(x) #x
 #define MIFC_STR(x) MIFC_STR0(x)
 const char* mifcref_kind(void)
 {
-  return "reference " MIFC_STR(MI_FIELDCALC_VERSION_MAJOR) "." MIFC_STR(MI_FIELDCALC_VERSION_MINOR) "." MIFC_STR(MI_FIELDCALC_VERSION_PATCH);
+  return MIFC_SHIM_KIND_NAME " " MIFC_STR(MI_FIELDCALC_VERSION_MAJOR) "." MIFC_STR(MI_FIELDCALC_VERSION_MINOR) "." MIFC_STR(MI_FIELDCALC_VERSION_PATCH);
 }
 
 } // extern "C"

@@ -50,6 +50,14 @@ std::vector<miutil::ValuesDefined> flag_vector(const int* flags, int n)
   Flag f(fdefined);   \
   return call
 
+// The reference's void operators cannot refuse: they return 1 here.  The drop-in's can fail (no device, a HIP
+// error) and its C++ API has only last_error() to say so, which every call clears on entry.
+#ifdef MIFC_SHIM_KIND_NAME
+#define SHIM_VOID_RESULT (fc::last_error()[0] == '\0')
+#else
+#define SHIM_VOID_RESULT 1
+#endif
+
 extern "C" {
 
 int mifcref_plevelthe(int nx, int ny, const float* t, const float* rh, float p, int compute, float* the, int* fdefined, float undef)
@@ -165,32 +173,32 @@ int mifcref_minvalueFields(int nx, int ny, const float* field1, const float* fie
 {
   Flag f(fdefined);
   fc::minvalueFields(nx, ny, field1, field2, fres, f.v, undef);
-  return 1;
+  return SHIM_VOID_RESULT;
 }
 int mifcref_maxvalueFields(int nx, int ny, const float* field1, const float* field2, float* fres, int* fdefined, float undef)
 {
   Flag f(fdefined);
   fc::maxvalueFields(nx, ny, field1, field2, fres, f.v, undef);
-  return 1;
+  return SHIM_VOID_RESULT;
 }
 int mifcref_minvalueFieldConst(int nx, int ny, const float* field1, float value, float* fres, int* fdefined, float undef)
 {
   Flag f(fdefined);
   fc::minvalueFieldConst(nx, ny, field1, value, fres, f.v, undef);
-  return 1;
+  return SHIM_VOID_RESULT;
 }
 int mifcref_maxvalueFieldConst(int nx, int ny, const float* field1, float value, float* fres, int* fdefined, float undef)
 {
   Flag f(fdefined);
   fc::maxvalueFieldConst(nx, ny, field1, value, fres, f.v, undef);
-  return 1;
+  return SHIM_VOID_RESULT;
 }
 #define SHIM_UNARY_VOID(name)                                                                              \
   int mifcref_##name(int nx, int ny, const float* field, float* fres, int* fdefined, float undef)          \
   {                                                                                                        \
     Flag f(fdefined);                                                                                      \
     fc::name(nx, ny, field, fres, f.v, undef);                                                             \
-    return 1;                                                                                              \
+    return SHIM_VOID_RESULT;                                                                               \
   }
 SHIM_UNARY_VOID(absvalueField)
 SHIM_UNARY_VOID(log10Field)
@@ -202,7 +210,7 @@ SHIM_UNARY_VOID(expField)
   {                                                                                                                 \
     Flag f(fdefined);                                                                                               \
     fc::name(nx, ny, field, value, fres, f.v, undef);                                                               \
-    return 1;                                                                                                       \
+    return SHIM_VOID_RESULT;                                                                                        \
   }
 SHIM_CONST_VOID(powerField)
 SHIM_CONST_VOID(replaceUndefined)

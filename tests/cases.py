@@ -315,6 +315,27 @@ def catalogue_cases(grids=GRIDS_EWISE, modes=MODES):
     return cases
 
 
+def order_cases(grids=((17, 9),), modes=MODES):
+    """Cases that exist so that every argument of an operator matters to its result (tests/test_gpu_cxx_dropin.py swaps
+    arguments and wants the result to change).  vesselIcingMertins: on a grid this small the winds of catalogue_cases
+    stay below 10.8 m/s, where the class is 0 whatever the air temperature; up to storm force here, every class occurs.
+    Kept apart from catalogue_cases, whose inputs the golden vectors record."""
+    cases = []
+    for (nx, ny), mode in itertools.product(grids, modes):
+        seed = 4177 * nx + ny
+        shape = (ny, nx)
+        u = synth.uniform(shape, seed + 1, -30.0, 30.0).astype(np.float32)
+        v = synth.uniform(shape, seed + 2, -30.0, 30.0).astype(np.float32)
+        tair = synth.uniform(shape, seed + 30, -25.0, 3.0).astype(np.float32)
+        tsst = synth.uniform(shape, seed + 31, -1.0, 8.0).astype(np.float32)
+        sal = synth.uniform(shape, seed + 16, 5.0, 38.0).astype(np.float32)
+        ice = synth.uniform(shape, seed + 32, 0.0, 0.5).astype(np.float32)
+        (tair_, tsst_, u_, v_, sal_, ice_), flag = _apply_mode([tair, tsst, u, v, sal, ice], mode, seed, _frac(nx, ny))
+        cases.append(dict(nx=nx, ny=ny, fdefined=flag, undef=UNDEF, op="vesselIcingMertins", args=[tair_, tsst_, u_, v_, sal_, ice_],
+                          label="vesselIcingMertins-storm-%dx%d-%s" % (nx, ny, mode)))
+    return cases
+
+
 def ensemble_cases(grids=((5, 4), (17, 9), (64, 48)), modes=MODES):
     """reductions over ensemble members."""
     cases = []

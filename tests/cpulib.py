@@ -3,7 +3,10 @@
 ``CpuLib("oracle")``  -> oracle/libmifc_oracle.so   (from-scratch restatement)
 ``CpuLib("ref")``     -> oracle/_ref/libmifc_ref.so (the real reference, compiled
                          from /root/reference by oracle/Makefile)
-Both export the flat ABI of oracle/oracle_abi.h.  Nothing outside tests/,
+``CpuLib("dropin")``  -> oracle/libmifc_dropin.so    (no checker: the PRODUCT's C++ API,
+                         libmi-fieldcalc.so over libmifc.so, behind the reference shim's
+                         wrappers; its calls run on the GPU and are what gets checked)
+All export the flat ABI of oracle/oracle_abi.h.  Nothing outside tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 """
 import ctypes
@@ -16,6 +19,7 @@ PATHS = {
     "oracle": (os.path.join(ROOT, "oracle", "libmifc_oracle.so"), "mifcorc_"),
     "ref": (os.path.join(ROOT, "oracle", "_ref", "libmifc_ref.so"), "mifcref_"),
     "ref_omp": (os.path.join(ROOT, "oracle", "_ref", "libmifc_ref_omp.so"), "mifcref_"),
+    "dropin": (os.path.join(ROOT, "oracle", "libmifc_dropin.so"), "mifcref_"),
 }
 
 ALL_DEFINED, NONE_DEFINED, SOME_DEFINED = 0, 1, 2
@@ -116,6 +120,12 @@ class CpuLib:
         if not os.path.exists(path):
             raise FileNotFoundError(path + " (run: make -C oracle)")
         self.which = which
+        if which == "dropin":
+            # the product library first, the way the package loads it (torch's HIP runtime before the system's):
+            # the shim then binds to that one copy of libmifc.so
+            import mi_fieldcalc_amd._capi as capi
+
+            capi.lib()
         self._lib = ctypes.CDLL(path)
         self._fn = {}
         self._sigs = dict(SIGS, **(ORACLE_ONLY if which == "oracle" else {}))
@@ -128,6 +138,11 @@ class CpuLib:
         kind = getattr(self._lib, prefix + "kind")
         kind.restype = _S
         self.kind = kind().decode()
+        if which == "dropin":  # the product's additions to the reference API, see oracle/ref_shim.cc
+            self._lib.mifcref_last_error.restype = _S
+            self._lib.mifcref_last_error.argtypes = []
+            self._lib.mifcref_neighbourFunctions.restype = _I
+            self._lib.mifcref_neighbourFunctions.argtypes = [_I, _I, _F, _F, _I, _I, _F, ctypes.c_void_p, _R]
 
     def call(self, name, nx, ny, *args, fdefined=SOME_DEFINED, undef=UNDEF, outs=None):
         """args in reference order (fields as numpy float32 arrays, scalars,
@@ -185,3 +200,17 @@ class CpuLib:
 
     def raw(self, name):
         return self._fn[name]
+
+    def last_error(self):
+        """fieldcalc::last_error() of the calling thread (drop-in only)."""
+        return self._lib.mifcref_last_error().decode()
+
+    def neighbourFunctions(self, nx, ny, field, constants, compute, fdefined=SOME_DEFINED, undef=UNDEF):
+        """The reference function the product declares but does not build (drop-in only).  Returns (ok, out, flag)."""
+        field = np.ascontiguousarray(field, dtype=np.float32)
+        consts = np.ascontiguousarray(constants, dtype=np.float32)
+        out = np.full((ny, nx), np.float32(-7777.0), dtype=np.float32)
+        fd = ctypes.c_int(int(fdefined))
+        ok = self._lib.mifcref_neighbourFunctions(nx, ny, field.ctypes.data, consts.ctypes.data, int(consts.size), int(compute), out.ctypes.data,
+                                                  ctypes.addressof(fd), float(undef))
+        return bool(ok), out, fd.value
