@@ -164,7 +164,7 @@ __device__ __forceinline__ float clamp_rh(float rh)
 // (BASELINE.json), not bit-exact.  The fused multiply-adds are explicit here
 // (accuracy, not parity, matters).  Arguments outside [2^-32, 2^32) -- no pressure
 // is -- and special values behave like powf with a positive non-integer exponent:
-// x<0 -> NaN, 0 -> 0, inf -> inf, NaN -> NaN (pow_kappa_rare, inline).
+// finite x<0 -> NaN, 0 -> 0, +-inf -> +inf, NaN -> NaN (pow_kappa_rare, inline).
 #include "mifc_kappa_tables.h"
 #define MIFC_POW_LOG_N 16
 #define MIFC_POW_EXP_N 32
@@ -307,12 +307,12 @@ __device__ __forceinline__ double pow_kappa_core(const PowTables& T, int ix)
 // brought into the table's range by exact scalings with 2^+-64, 2^(+-64 kappa) multiplied back in double.
 __device__ __forceinline__ float pow_kappa_rare(const PowTables& T, float x)
 {
+  if (__builtin_fabsf(x) == __int_as_float(0x7f800000))
+    return __int_as_float(0x7f800000); // -inf too: powf(-inf, y) is +inf for a positive y that is no odd integer
   if (x != x || x < 0.f)
     return __int_as_float(0x7fc00000);
   if (x == 0.f)
     return 0.f;
-  if (x == __int_as_float(0x7f800000))
-    return x;
   float xs;
   double c;
   if (x < 1.f) {
