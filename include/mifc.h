@@ -367,6 +367,50 @@ enum { MIFC_QUANTILE_LOWER = 0, MIFC_QUANTILE_LINEAR = 1 };
 int mifc_ensembleQuantiles(mifc_ctx* ctx, int method, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nmem,
                            const float* percentiles, int nq, float* const* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: interpolation of level batches to constant surfaces ------------------------------------------
+ * Not a miutil::fieldcalc function: the reference leaves the step from model levels to the pressure (or height, or
+ * isentropic) surfaces its plevel* / ilevel* operators work on to its caller.  nfields fields of [nlev][ny][nx] and one
+ * coordinate per level and cell go in, nfields fields of [ntargets][ny][nx] come out.  For each cell i and target t,
+ * ct = targets[t]:
+ *   1. Coordinate.  mifc_vinterp_hlevels: c_k = alevel[k] + blevel[k] * ps[i], evaluated in float exactly like the
+ *      reference's p_hlevel (FieldCalculations.cc:303): float product, then float sum, no contraction; every c_k of the
+ *      cell is defined where is_defined(fdef_ps == ALL_DEFINED, ps[i], undef).  mifc_vinterp_fields: c_k = coord[k][i],
+ *      defined where is_defined(fdef_coord[k] == ALL_DEFINED, c_k, undef).
+ *   2. Bracket.  The first k in index order, 0 <= k < nlev - 1, with c_k and c_{k+1} both defined and
+ *      min(c_k, c_{k+1}) <= ct <= max(c_k, c_{k+1}).  No monotonicity and no level order (top-down, bottom-up) is
+ *      assumed.  A NaN coordinate (which can only get in through an ALL_DEFINED flag) fails both comparisons and never
+ *      brackets.  Without a bracket every field is undef at (t, i): above the top, below the ground.
+ *   3. Values.  Field f needs x_k and x_{k+1} defined, each under is_defined(fdefined_in[f * nlev + level] ==
+ *      ALL_DEFINED, x, undef); otherwise its result is undef.
+ *   4. MIFC_VINTERP_LOG with min(c_k, c_{k+1}) <= 0 at the bracket: undef.
+ *   5. c_k == c_{k+1}: the result is x_k bit for bit, nothing is divided.
+ *   6. Otherwise the weight, in double, every operation rounded on its own (no contraction):
+ *      MIFC_VINTERP_LINEAR = 0: w = ((double)ct - (double)c_k) / ((double)c_{k+1} - (double)c_k);
+ *      MIFC_VINTERP_LOG = 1: the same with log() of each of the three values, in double;
+ *      and the result is (float)((double)x_k + w * ((double)x_{k+1} - (double)x_k)).
+ *   7. Flags.  fdefined_out[f * ntargets + t] = checkDefined(cells that rules 2 to 4 left undef, nx * ny).
+ * LINEAR is bit for bit this definition.  LOG depends on the device's double log(): a result is the definition's
+ * float or its neighbour (the weight is off by a few ulp of double at most), undef cells and flags are exact.
+ * Arguments: `fields` is a HOST array of nfields pointers, each to [nlev][ny][nx]; `fdefined_in` a HOST
+ * int[nfields * nlev], field-major (f * nlev + k), NULL = all SOME_DEFINED; `alevel`, `blevel` (HOST float[nlev]) and
+ * `targets` (HOST float[ntargets]) are host arrays; `ps` is [ny][nx], `coord` [nlev][ny][nx], `fdef_coord` a HOST
+ * int[nlev], NULL = all SOME_DEFINED; `fres` is a HOST array of nfields pointers, each to [ntargets][ny][nx];
+ * `fdefined_out` a HOST int[nfields * ntargets], field-major (f * ntargets + t).
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; nfields outside
+ * 1..8; ntargets outside 1..64; a negative nx or ny; a null pointer; an unknown method; a NaN target; LOG with a target
+ * <= 0; hybrid form only: a level whose (alevel, blevel) the reference's bad_hlevel (FieldCalculations.cc:298) rejects;
+ * an output that overlaps an input, the coordinate, ps or another output; a call made while a mifc_graph capture is open.
+ * memkind works as everywhere else; host memory works at any size: columns are independent, so the call stages a band of
+ * rows at a time, MIFC_VINTERP_CHUNK_MIB of device memory (default 256).  Every input level is read once per 32
+ * targets. */
+enum { MIFC_VINTERP_LINEAR = 0, MIFC_VINTERP_LOG = 1 };
+int mifc_vinterp_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                         const float* ps, int fdef_ps, const float* alevel, const float* blevel, const float* targets, int ntargets,
+                         int method, float* const* fres, int* fdefined_out, float undef, int memkind);
+int mifc_vinterp_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, const float* targets,
+                        int ntargets, int method, float* const* fres, int* fdefined_out, float undef, int memkind);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

@@ -629,6 +629,79 @@ class Context:
             raise RuntimeError("mifc_ensembleQuantiles: " + self.last_error())
         return (out if _is_torch(out) else oa.keep), (int(fd[0]) if len(shape) == 2 else fd)
 
+    # ------------------------------------------------------ level batches to constant surfaces (EXTENSION)
+    def _vinterp(self, name, fields, coord, coord_args, targets, method, fdefined_in, undef, out):
+        code = {"linear": 0, "log": 1}.get(method, -1) if isinstance(method, str) else int(method)
+        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
+        if one:
+            batches = [fields]
+        elif isinstance(fields, np.ndarray) or _is_torch(fields):
+            batches = [fields[f] for f in range(fields.shape[0])]
+        else:
+            batches = list(fields)
+        if not batches:
+            raise ValueError("no fields")
+        fa = [_Arg(b) for b in batches]
+        shape = tuple(fa[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be (nlev, ny, nx) batches")
+        if not _same_shape(fa, shape):
+            raise ValueError("every field must have the shape %s" % (shape,))
+        nlev, ny, nx = shape
+        ca = _Arg(coord)
+        want = (ny, nx) if name == "mifc_vinterp_hlevels" else shape
+        if tuple(ca.shape) != want:
+            raise ValueError("the coordinate must have the shape %s" % (want,))
+        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.float32).ravel())
+        nt, nf = int(tg.size), len(fa)
+        out_shape = (nt, ny, nx) if one else (nf, nt, ny, nx)
+        if out is None:
+            out = _empty_like(batches[0], out_shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != out_shape:
+            raise ValueError("out must have shape %s" % (out_shape,))
+        mk = _memkind(fa + [ca, oa], self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * nf)(*[oa.addr + f * nt * ny * nx * 4 for f in range(nf)])
+        flags = None
+        if fdefined_in is not None:
+            f = np.asarray(fdefined_in, dtype=np.int32)
+            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
+                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
+            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        fd = np.zeros((nf, nt), np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, ca.addr] + coord_args + [tg, nt, code, ctypes.addressof(outs), fd, float(undef), mk]
+        if not self._call(name, args):
+            raise RuntimeError(name + ": " + self.last_error())
+        res = out if _is_torch(out) else oa.keep
+        return (res, fd[0]) if one else (res, fd)
+
+    def vinterp_hlevels(self, fields, ps, alevel, blevel, targets, method="linear", fdefined_in=None, fdef_ps=SOME_DEFINED, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vinterp_hlevels): hybrid-level batches interpolated to the surfaces where the
+        coordinate alevel[k] + blevel[k] * ps takes the values `targets` (pressure surfaces, say), linearly in the
+        coordinate ("linear") or in its logarithm ("log").  fields: a list of (nlev, ny, nx) numpy arrays (host memory)
+        or CUDA tensors (device), or one stacked (nf, nlev, ny, nx); ps: (ny, nx); fdefined_in: flags (nf, nlev), or one
+        per field; None: SOME_DEFINED.  Returns (out (nf, ntargets, ny, nx), flags int32 (nf, ntargets)); with ONE
+        (nlev, ny, nx) batch for `fields` the leading axis is dropped from both.  A refused call raises RuntimeError."""
+        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
+        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
+        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
+        if al.size != nlev or bl.size != nlev:
+            raise ValueError("alevel and blevel must hold one value per level")
+        return self._vinterp("mifc_vinterp_hlevels", fields, ps, [int(fdef_ps), al, bl], targets, method, fdefined_in, undef, out)
+
+    def vinterp_fields(self, fields, coord, targets, method="linear", fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vinterp_fields): as vinterp_hlevels, the coordinate given as a batch
+        (nlev, ny, nx) like the fields (pressure on other level types, height, potential temperature ...);
+        fdef_coord: one flag per level, None: SOME_DEFINED."""
+        fc_ = None
+        if fdef_coord is not None:
+            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
+            if fc_.size != int(_Arg(coord).shape[0]):
+                raise ValueError("fdef_coord must hold one flag per level")
+        return self._vinterp("mifc_vinterp_fields", fields, coord, [fc_], targets, method, fdefined_in, undef, out)
+
     def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
         """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability
         over the same members in one pass, each bit for bit what its single-field function returns per level.

@@ -124,6 +124,9 @@ SIGNATURES = {
     "mifc_probability": ("i", ["ctx", "i", "i", "i", "p", "p", "i", "p", "i", "p", "pi", "f", "i"]),
     # EXTENSION: percentiles across members (fields, fres: host tables of pointers; percentiles: host float array)
     "mifc_ensembleQuantiles": ("i", ["ctx", "i", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "f", "i"]),
+    # EXTENSION: level batches to constant surfaces (fields, fres: host tables of pointers; alevel, blevel, targets: host arrays)
+    "mifc_vinterp_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "p", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_vinterp_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "i", "i", "p", "pi", "f", "i"]),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

@@ -300,6 +300,47 @@ inline bool ensemble_levels_vec4(const EnsLevelsParams& P)
 }
 hipError_t launch_ensemble_levels(const EnsLevelsParams& prm, hipStream_t stream);
 
+// ------------------------------------ level batches to constant surfaces (mifc_vinterp.hip), EXTENSION
+// One launch walks the `nlev` levels of `n` columns once and serves up to VINTERP_PASS targets; the host launches a second
+// pass for targets beyond that.  Field f's level k is fields[f] + k * in_stride, its result for call target t
+// out[f] + t * out_stride; `coord` is ps (hybrid: n floats) or the coordinate batch (field: laid out like a field).
+// The per-level scalars sit in a device table (`ab`: alevel[nlev] then blevel[nlev]; `lev_bits[k]`: bit f = field f is
+// flagged ALL_DEFINED at level k, bit VINTERP_COORD_BIT = the coordinate is), the targets of the pass in the kernel
+// arguments.  vec4: four cells per lane through 16-byte loads -- every pointer 16-byte aligned, both strides multiples
+// of 4, and the four floats of a lane's group readable even where the group straddles n (the staged band is padded; a
+// device batch qualifies when n is a multiple of 4).  Otherwise one cell per lane.
+const int VINTERP_MAX_FIELDS = 8, VINTERP_PASS = 32, VINTERP_MAX_TARGETS = 64, VINTERP_COORD_BIT = 8;
+struct VinterpParams
+{
+  int hybrid;     // coordinate kind: 1 = alevel + blevel * ps, 0 = field
+  int method;     // MIFC_VINTERP_LINEAR / MIFC_VINTERP_LOG
+  int nfields;    // 1 .. VINTERP_MAX_FIELDS
+  int n;          // columns of this launch
+  int nlev;       // >= 2
+  int nt;         // targets of this pass, 1 .. VINTERP_PASS
+  int t0;         // the call's target of the pass' target 0 (outputs, counters)
+  int nt_call;    // targets of the whole call: the distance between the counters of two fields
+  int vec4;
+  int ps_all;     // hybrid: fdef_ps == ALL_DEFINED
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[VINTERP_MAX_FIELDS];
+  float* out[VINTERP_MAX_FIELDS];
+  const float* coord;
+  const float* ab;
+  const unsigned int* lev_bits;
+  u64* n_undefined;                // [nfields][nt_call], zeroed by the caller
+  float target[VINTERP_PASS];      // ct
+  int target_key[VINTERP_PASS];    // ct + 0.f as an order-preserving int (vinterp_key): the wave-uniform pre-filter compares integers
+  double target_log[VINTERP_PASS]; // LOG: log((double)ct), from the host
+};
+// float bits -> int with the same order as the floats (no NaN among the operands; -0 must have been turned into +0)
+__host__ __device__ inline int vinterp_key(int bits)
+{
+  return bits ^ ((bits >> 31) & 0x7fffffff);
+}
+hipError_t launch_vinterp(const VinterpParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
