@@ -411,6 +411,64 @@ int mifc_vinterp_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* co
                         const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, const float* targets,
                         int ntargets, int method, float* const* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: layer integrals, means and extremes of level batches -----------------------------------------
+ * Not a miutil::fieldcalc function: the reference leaves every reduction over levels (precipitable water, a layer-mean
+ * wind, the maximum wind of a layer and where it sits, a pressure-weighted mean between two surfaces) to a host loop of
+ * its caller.  nfields fields of [nlev][ny][nx] and one coordinate per level and cell go in -- the same inputs as
+ * mifc_vinterp_* above --, fres[f] is [nproducts][ny][nx].  `products` is a HOST array of distinct codes:
+ * MIFC_VLAYER_INTEGRAL, _MEAN, _MAX, _MIN, _COORD_OF_MAX, _COORD_OF_MIN.  The layer is [lo, hi] in the coordinate;
+ * +-infinity means open; lo_field / hi_field are optional [ny][nx] fields of the same memory kind that give the bound
+ * per cell (ps - 100 for the lowest 100 hPa), NULL = use the scalar.  Per cell i:
+ *   1. Coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it, in both forms (hybrid: the float product, then the
+ *      float sum).  A coordinate is usable when it is defined by that rule AND is not NaN.  If any c_k of the cell is
+ *      not usable, every product of every field is undef at i.
+ *   2. Bounds.  L = lo_field[i] if given, else lo; H likewise.  A bound from a field is always tested: NaN or == undef
+ *      makes the cell undef.  !(L < H): the cell is undef.
+ *   3. Pairs.  For k = 0 .. nlev - 2 in index order: p = (c_k <= c_{k+1}) ? c_k : c_{k+1}, q the other one;
+ *      a = (p >= L) ? p : L, b = (q <= H) ? q : H.  The pair takes part iff a < b.  No level order and no monotonicity
+ *      is assumed; overlapping pairs of a non-monotone column each count.  If no pair takes part, the cell is undef for
+ *      every field.
+ *   4. Values.  Field f needs x_k and x_{k+1} defined at EVERY pair that takes part, each under
+ *      is_defined(fdefined_in[f * nlev + level] == ALL_DEFINED, x, undef); otherwise all products of f are undef at i (an
+ *      integral with a hole in it is a wrong number, not a partial one).  Levels outside the layer do not matter.
+ *   5. End values, in double, every operation rounded on its own.  For an end e of {a, b}: e == c_k: v = (double)x_k;
+ *      else e == c_{k+1}: v = (double)x_{k+1}; else w = ((double)e - c_k) / ((double)c_{k+1} - c_k) and
+ *      v = x_k + w * (x_{k+1} - x_k).  d = (double)b - (double)a; ext += d; acc_f += ((v_a + v_b) * 0.5) * d.
+ *   6. Products.  INTEGRAL = (float)acc_f.  MEAN = (float)(acc_f / ext).  The extremes work on (float)v, the end nearer
+ *      level k first and then the other, in pair order: the first candidate initialises both extremes, a later one
+ *      replaces the maximum on strict > and the minimum on strict <, so the first occurrence wins and a NaN that comes
+ *      first stays.  COORD_OF_MAX / COORD_OF_MIN is the float e of the winning candidate: always a level's coordinate or
+ *      a bound, never computed.
+ *   7. Flags.  fdefined_out[f * nproducts + p] = checkDefined(cells that rules 1 to 4 left undef, nx * ny): the same
+ *      for every product of a field.  A computed NaN or infinity is not counted.
+ * Results are bit for bit this definition (restated in numpy in tests/vlayer_restate.py).
+ * Arguments as for mifc_vinterp_*: `fields`, `fres` HOST arrays of nfields pointers; `fdefined_in` HOST int[nfields *
+ * nlev] or NULL; `alevel`, `blevel` HOST float[nlev]; `fdef_coord` HOST int[nlev] or NULL; `fdefined_out` HOST
+ * int[nfields * nproducts], field-major.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; nfields outside
+ * 1..8; nproducts outside 1..6; an unknown or repeated product code; a negative nx or ny; a null pointer that is
+ * required; with both bounds scalar !(lo < hi), with one scalar bound that scalar NaN; hybrid form only: a level whose
+ * (alevel, blevel) the reference's bad_hlevel (FieldCalculations.cc:298) rejects; an output that overlaps an input, the
+ * coordinate, ps, a bound field or another output; a call made while a mifc_graph capture is open.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time,
+ * MIFC_VLAYER_CHUNK_MIB of device memory (default 256).  Every field level is read once per call. */
+enum {
+  MIFC_VLAYER_INTEGRAL = 1,
+  MIFC_VLAYER_MEAN = 2,
+  MIFC_VLAYER_MAX = 3,
+  MIFC_VLAYER_MIN = 4,
+  MIFC_VLAYER_COORD_OF_MAX = 5,
+  MIFC_VLAYER_COORD_OF_MIN = 6
+};
+int mifc_vlayer_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* ps, int fdef_ps, const float* alevel, const float* blevel, float lo, float hi,
+                        const float* lo_field, const float* hi_field, const int* products, int nproducts, float* const* fres,
+                        int* fdefined_out, float undef, int memkind);
+int mifc_vlayer_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, float lo, float hi,
+                       const float* lo_field, const float* hi_field, const int* products, int nproducts, float* const* fres,
+                       int* fdefined_out, float undef, int memkind);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

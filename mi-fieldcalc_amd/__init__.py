@@ -30,6 +30,8 @@ __all__ = ["Context", "SlabPlan", "Graph", "PreparedCalls", "ALL_DEFINED", "NONE
 ENS_SUM, ENS_MEAN, ENS_STDDEV, ENS_EXTREME, ENS_PROBABILITY = 0, 1, 2, 3, 4
 _ENS_EXTREMES = {"max": 1, "min": 2, "argmax": 3, "argmin": 4}
 _ENS_MAX_PROBABILITIES = 8
+# the product codes of mifc_vlayer_* (include/mifc.h, MIFC_VLAYER_*) and the names Context.vlayer_* takes for them
+VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max": 5, "coord_of_min": 6}
 
 
 def ensemble_products(products):
@@ -701,6 +703,92 @@ class Context:
             if fc_.size != int(_Arg(coord).shape[0]):
                 raise ValueError("fdef_coord must hold one flag per level")
         return self._vinterp("mifc_vinterp_fields", fields, coord, [fc_], targets, method, fdefined_in, undef, out)
+
+    # ------------------------------------------ layer integrals, means and extremes of level batches (EXTENSION)
+    def _vlayer(self, name, fields, coord, coord_args, products, lo, hi, fdefined_in, undef, out):
+        codes = [VLAYER_PRODUCTS.get(p, -1) if isinstance(p, str) else int(p) for p in ([products] if isinstance(products, (str, int)) else products)]
+        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
+        if one:
+            batches = [fields]
+        elif isinstance(fields, np.ndarray) or _is_torch(fields):
+            batches = [fields[f] for f in range(fields.shape[0])]
+        else:
+            batches = list(fields)
+        if not batches:
+            raise ValueError("no fields")
+        fa = [_Arg(b) for b in batches]
+        shape = tuple(fa[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be (nlev, ny, nx) batches")
+        if not _same_shape(fa, shape):
+            raise ValueError("every field must have the shape %s" % (shape,))
+        nlev, ny, nx = shape
+        ca = _Arg(coord)
+        want = (ny, nx) if name == "mifc_vlayer_hlevels" else shape
+        if tuple(ca.shape) != want:
+            raise ValueError("the coordinate must have the shape %s" % (want,))
+        bounds, scalars, ptrs = [], [], []
+        for b in (lo, hi):  # a number, or a (ny, nx) field of per-cell bounds
+            if (isinstance(b, np.ndarray) and b.ndim > 0) or _is_torch(b):
+                ba = _Arg(b)
+                if tuple(ba.shape) != (ny, nx):
+                    raise ValueError("a bound given as a field must have the shape %s" % ((ny, nx),))
+                bounds.append(ba)
+                scalars.append(0.0)
+                ptrs.append(ba.addr)
+            else:
+                scalars.append(float(b))
+                ptrs.append(None)
+        np_, nf = len(codes), len(fa)
+        out_shape = (np_, ny, nx) if one else (nf, np_, ny, nx)
+        if out is None:
+            out = _empty_like(batches[0], out_shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != out_shape:
+            raise ValueError("out must have shape %s" % (out_shape,))
+        mk = _memkind(fa + [ca, oa] + bounds, self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * nf)(*[oa.addr + f * np_ * ny * nx * 4 for f in range(nf)])
+        flags = None
+        if fdefined_in is not None:
+            f = np.asarray(fdefined_in, dtype=np.int32)
+            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
+                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
+            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        pc = np.ascontiguousarray(codes, dtype=np.int32)
+        fd = np.zeros((nf, np_), np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, ca.addr] + coord_args + scalars + ptrs + [pc, np_, ctypes.addressof(outs), fd, float(undef), mk]
+        if not self._call(name, args):
+            raise RuntimeError(name + ": " + self.last_error())
+        res = out if _is_torch(out) else oa.keep
+        return (res, fd[0]) if one else (res, fd)
+
+    def vlayer_hlevels(self, fields, ps, alevel, blevel, products, lo=-np.inf, hi=np.inf, fdefined_in=None, fdef_ps=SOME_DEFINED, undef=UNDEF,
+                       out=None):
+        """EXTENSION (include/mifc.h, mifc_vlayer_hlevels): integrals, means and extremes of hybrid-level batches over
+        the layer lo <= c <= hi of the coordinate c = alevel[k] + blevel[k] * ps, in one pass over the levels.
+        fields, ps, fdefined_in: as vinterp_hlevels takes them.  products: names ("integral", "mean", "max", "min",
+        "coord_of_max", "coord_of_min") or MIFC_VLAYER_* codes, each at most once.  lo, hi: a number (+-inf: open) or a
+        (ny, nx) array / tensor of per-cell bounds.  Returns (out (nf, nproducts, ny, nx), flags int32
+        (nf, nproducts)); with ONE (nlev, ny, nx) batch for `fields` the leading axis is dropped from both.  A refused
+        call raises RuntimeError."""
+        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
+        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
+        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
+        if al.size != nlev or bl.size != nlev:
+            raise ValueError("alevel and blevel must hold one value per level")
+        return self._vlayer("mifc_vlayer_hlevels", fields, ps, [int(fdef_ps), al, bl], products, lo, hi, fdefined_in, undef, out)
+
+    def vlayer_fields(self, fields, coord, products, lo=-np.inf, hi=np.inf, fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vlayer_fields): as vlayer_hlevels, the coordinate given as a batch
+        (nlev, ny, nx) like the fields; fdef_coord: one flag per level, None: SOME_DEFINED."""
+        fc_ = None
+        if fdef_coord is not None:
+            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
+            if fc_.size != int(_Arg(coord).shape[0]):
+                raise ValueError("fdef_coord must hold one flag per level")
+        return self._vlayer("mifc_vlayer_fields", fields, coord, [fc_], products, lo, hi, fdefined_in, undef, out)
 
     def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
         """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability

@@ -127,6 +127,8 @@ SIGNATURES = {
     # EXTENSION: level batches to constant surfaces (fields, fres: host tables of pointers; alevel, blevel, targets: host arrays)
     "mifc_vinterp_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_vinterp_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_vlayer_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "f", "f", "p", "p", "pi", "i", "p", "pi", "f", "i"]),
+    "mifc_vlayer_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "f", "f", "p", "p", "pi", "i", "p", "pi", "f", "i"]),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

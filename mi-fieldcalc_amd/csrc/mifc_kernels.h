@@ -341,6 +341,44 @@ __host__ __device__ inline int vinterp_key(int bits)
 }
 hipError_t launch_vinterp(const VinterpParams& prm, hipStream_t stream);
 
+// ------------------------------------ layer integrals, means and extremes of level batches (mifc_vlayer.hip), EXTENSION
+// One launch walks the `nlev` levels of `n` columns once for up to VLAYER_PASS fields and stores, per field, the products
+// whose `slot` is not negative: product code p (MIFC_VLAYER_*, 1..6) goes to out[f] + slot[p - 1] * out_stride.  The host
+// launches again for the fields beyond VLAYER_PASS (the coordinate and the bounds are read again, every field level once).
+// VLAYER_PASS is the most a launch takes; carrying the sums AND the extremes it takes two (vlayer_pass_fields: the field
+// counts at which every instance keeps two waves per SIMD without a spill).
+// Inputs, `coord`, the level table (`ab`, `lev_bits`: bit f0 + f = field f of the launch is flagged ALL_DEFINED at level
+// k, bit VINTERP_COORD_BIT = the coordinate is) and vec4 as in VinterpParams; lo_field / hi_field: per-cell bounds (n
+// floats each, on the 16-byte grid for vec4) or null = the scalar.  `group`: what the walk carries -- VLAYER_SUMS
+// (INTEGRAL, MEAN), VLAYER_EXTREMES (the other four) or both.
+const int VLAYER_MAX_FIELDS = 8, VLAYER_PASS = 4, VLAYER_PRODUCTS = 6, VLAYER_SUMS = 1, VLAYER_EXTREMES = 2;
+constexpr int vlayer_pass_fields(int group)
+{
+  return group == (VLAYER_SUMS | VLAYER_EXTREMES) ? 2 : VLAYER_PASS;
+}
+struct VlayerParams
+{
+  int hybrid;  // coordinate kind: 1 = alevel + blevel * ps, 0 = field
+  int group;   // VLAYER_SUMS | VLAYER_EXTREMES
+  int nfields; // of this launch, 1 .. VLAYER_PASS
+  int f0;      // the call's field of the launch's field 0 (level bits, counters)
+  int n;       // columns of this launch
+  int nlev;    // >= 2
+  int vec4;
+  int ps_all;  // hybrid: fdef_ps == ALL_DEFINED
+  float undef, lo, hi;
+  long in_stride, out_stride;
+  const float* fields[VLAYER_PASS];
+  float* out[VLAYER_PASS];
+  const float* coord;
+  const float *lo_field, *hi_field;
+  const float* ab;
+  const unsigned int* lev_bits;
+  u64* n_undefined; // [the call's nfields], zeroed by the caller
+  int slot[VLAYER_PRODUCTS];
+};
+hipError_t launch_vlayer(const VlayerParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
