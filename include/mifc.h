@@ -469,6 +469,61 @@ int mifc_vlayer_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
                        const float* lo_field, const float* hi_field, const int* products, int nproducts, float* const* fres,
                        int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: vertical derivatives of level batches, with vector magnitude ---------------------------------
+ * Not a miutil::fieldcalc function: static stability (d theta / dp), the lapse rate, the vertical wind shear, dp / d theta
+ * for isentropic potential vorticity, the thermal wind -- the reference leaves every difference across levels to a host
+ * loop of its caller.  nfields fields of [nlev][ny][nx] and one coordinate per level go in -- the inputs of
+ * mifc_vinterp_* and mifc_vlayer_* above, or (mifc_vderiv_levels) one coordinate value per level: pressure levels, the
+ * `targets` of an earlier mifc_vinterp_* call --, fres[f] is [nlev][ny][nx]: one derivative per input level.  fmag is
+ * optional: nfields / 2 outputs [nlev][ny][nx], fmag[j] the magnitude of the derivative of the vector whose components
+ * are the fields 2j and 2j + 1 (u, v: the shear).  fres may be NULL as a whole when fmag is given: only the magnitudes are
+ * written.  Per cell i, field f and output level k:
+ *   1. Coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it (hybrid: the float product, then the float sum);
+ *      mifc_vderiv_levels: c_k = levels[k], always defined.  A coordinate is usable when it is defined by that rule AND
+ *      is not NaN.  Unlike mifc_vlayer_*, an unusable coordinate affects only the levels that touch it.
+ *   2. Points.  Point m is usable for f when c_m is usable and x_m passes is_defined(fdefined_in[f * nlev + m] ==
+ *      ALL_DEFINED, x_m, undef).  If point k itself is not usable the result is undef.
+ *   3. Sides.  The lower side k - 1 takes part when k > 0, point k - 1 is usable and c_{k-1} != c_k; the upper side k + 1
+ *      likewise with k < nlev - 1.  No level order and no monotonicity is assumed.
+ *   4. Both sides take part.  All in double, every operation rounded on its own (no contraction).
+ *      MIFC_VDERIV_CENTRED = 0: dc = c_{k+1} - c_{k-1}; dc == 0 (a folded column): undef; otherwise w = 1.0 / dc and
+ *      r = (x_{k+1} - x_{k-1}) * w.
+ *      MIFC_VDERIV_WEIGHTED = 1 (second order on uneven spacing): h1 = c_k - c_{k-1}, h2 = c_{k+1} - c_k, s = h1 + h2;
+ *      s == 0: undef; otherwise w1 = h2 / (h1 * s), w2 = h1 / (h2 * s), r = (x_k - x_{k-1}) * w1 + (x_{k+1} - x_k) * w2.
+ *   5. One side takes part (the first and the last level, the level next to a hole or to the ground of a pressure-level
+ *      batch), both methods: with (a, b) the two points in index order w = 1.0 / (c_b - c_a), r = (x_b - x_a) * w.
+ *   6. No side takes part: undef.
+ *   7. The result is (float)r.  A computed NaN or infinity is a value: not undef, not counted.
+ *   8. Magnitude.  fmag[j] is the reference's absval (math_util.h:57) of the two float results, sqrtf(a * a + b * b) in
+ *      float, uncontracted, the square root correctly rounded; undef where either component is undef by rules 2 to 6.
+ *   9. Flags.  fdefined_out[f * nlev + k] = checkDefined(cells left undef at level k, nx * ny); fdefined_mag[j * nlev + k]
+ *      the same for the magnitude.
+ * The weights depend on the coordinate only: the divisions are paid once per cell and level however many fields the
+ * call carries, in the `levels` form once per level.  Results are bit for bit this definition (restated in numpy in
+ * tests/vderiv_restate.py).
+ * Arguments as for mifc_vinterp_*: `fields`, `fres` HOST arrays of nfields pointers, `fmag` a HOST array of nfields / 2
+ * pointers; `fdefined_in` HOST int[nfields * nlev] or NULL; `alevel`, `blevel`, `levels` HOST float[nlev]; `fdef_coord`
+ * HOST int[nlev] or NULL; `fdefined_out` HOST int[nfields * nlev], `fdefined_mag` HOST int[(nfields / 2) * nlev].
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; nfields outside
+ * 1..8; a negative nx or ny; an unknown method; a null pointer that is required; fres and fmag both NULL; fmag with an
+ * odd nfields; fmag without fdefined_mag; fres without fdefined_out; hybrid form: a level whose (alevel, blevel) the
+ * reference's bad_hlevel (FieldCalculations.cc:298) rejects; `levels` form: a NaN level; an output that overlaps an
+ * input, the coordinate, ps or another output by byte range (in-place is not offered); a call made while a mifc_graph
+ * capture is open.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time,
+ * MIFC_VDERIV_CHUNK_MIB of device memory (default 256).  Every input level is read once and every output level written
+ * once per call. */
+enum { MIFC_VDERIV_CENTRED = 0, MIFC_VDERIV_WEIGHTED = 1 };
+int mifc_vderiv_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* ps, int fdef_ps, const float* alevel, const float* blevel, int method, float* const* fres,
+                        int* fdefined_out, float* const* fmag, int* fdefined_mag, float undef, int memkind);
+int mifc_vderiv_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, int method,
+                       float* const* fres, int* fdefined_out, float* const* fmag, int* fdefined_mag, float undef, int memkind);
+int mifc_vderiv_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* levels /* HOST float[nlev] */, int method, float* const* fres, int* fdefined_out,
+                       float* const* fmag, int* fdefined_mag, float undef, int memkind);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

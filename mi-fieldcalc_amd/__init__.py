@@ -32,6 +32,8 @@ _ENS_EXTREMES = {"max": 1, "min": 2, "argmax": 3, "argmin": 4}
 _ENS_MAX_PROBABILITIES = 8
 # the product codes of mifc_vlayer_* (include/mifc.h, MIFC_VLAYER_*) and the names Context.vlayer_* takes for them
 VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max": 5, "coord_of_min": 6}
+# the methods of mifc_vderiv_* (MIFC_VDERIV_*)
+VDERIV_METHODS = {"centred": 0, "weighted": 1}
 
 
 def ensemble_products(products):
@@ -789,6 +791,118 @@ class Context:
             if fc_.size != int(_Arg(coord).shape[0]):
                 raise ValueError("fdef_coord must hold one flag per level")
         return self._vlayer("mifc_vlayer_fields", fields, coord, [fc_], products, lo, hi, fdefined_in, undef, out)
+
+    # ------------------------------------------ vertical derivatives of level batches, vector magnitude (EXTENSION)
+    def _vderiv(self, name, fields, coord, coord_args, method, magnitude, fdefined_in, undef, out):
+        code = VDERIV_METHODS.get(method, -1) if isinstance(method, str) else int(method)
+        if magnitude not in (None, "also", "only"):
+            raise ValueError('magnitude must be None, "also" or "only"')
+        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
+        if one:
+            batches = [fields]
+        elif isinstance(fields, np.ndarray) or _is_torch(fields):
+            batches = [fields[f] for f in range(fields.shape[0])]
+        else:
+            batches = list(fields)
+        if not batches:
+            raise ValueError("no fields")
+        fa = [_Arg(b) for b in batches]
+        shape = tuple(fa[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be (nlev, ny, nx) batches")
+        if not _same_shape(fa, shape):
+            raise ValueError("every field must have the shape %s" % (shape,))
+        nlev, ny, nx = shape
+        nf = len(fa)
+        nm = nf // 2
+        others = []
+        if name == "mifc_vderiv_levels":
+            lv = np.ascontiguousarray(np.asarray(coord, dtype=np.float32).ravel())
+            if lv.size != nlev:
+                raise ValueError("levels must hold one value per level")
+            coord_arg = lv
+        else:
+            ca = _Arg(coord)
+            want = (ny, nx) if name == "mifc_vderiv_hlevels" else shape
+            if tuple(ca.shape) != want:
+                raise ValueError("the coordinate must have the shape %s" % (want,))
+            coord_arg = ca.addr
+            others.append(ca)
+        want_out, want_mag = magnitude != "only", magnitude is not None
+        given = list(out) if isinstance(out, (tuple, list)) else [out]
+        if want_out and want_mag and len(given) == 1:
+            given = [given[0], None]
+        if len(given) != (2 if want_out and want_mag else 1):
+            raise ValueError('out must be one array or tensor, or (out, mag) with magnitude="also"')
+        shapes = ([shape if one else (nf,) + shape] if want_out else []) + ([(nm,) + shape] if want_mag else [])
+        res = []
+        for o, s in zip(given, shapes):
+            if o is None:
+                o = _empty_like(batches[0], s)
+            oa = _Arg(o, output=True)
+            if tuple(oa.shape) != tuple(s):
+                raise ValueError("out must have shape %s" % (s,))
+            res.append((o, oa))
+        mk = _memkind(fa + others + [oa for _, oa in res], self.device)
+        self._bind_stream(mk)
+        batch_bytes = nlev * ny * nx * 4
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = mags = fd = mfd = None
+        if want_out:
+            outs = (ctypes.c_void_p * nf)(*[res[0][1].addr + f * batch_bytes for f in range(nf)])
+            fd = np.zeros((nf, nlev), np.int32)
+        if want_mag:
+            mags = (ctypes.c_void_p * max(nm, 1))(*[res[-1][1].addr + j * batch_bytes for j in range(nm)])
+            mfd = np.zeros((nm, nlev), np.int32)
+        flags = None
+        if fdefined_in is not None:
+            f = np.asarray(fdefined_in, dtype=np.int32)
+            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
+                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
+            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, coord_arg] + coord_args + [
+            code, ctypes.addressof(outs) if want_out else None, fd, ctypes.addressof(mags) if want_mag else None, mfd, float(undef), mk]
+        if not self._call(name, args):
+            raise RuntimeError(name + ": " + self.last_error())
+        ret = []
+        if want_out:
+            ret += [res[0][0] if _is_torch(res[0][0]) else res[0][1].keep, fd[0] if one else fd]
+        if want_mag:
+            ret += [res[-1][0] if _is_torch(res[-1][0]) else res[-1][1].keep, mfd]
+        return tuple(ret)
+
+    def vderiv_hlevels(self, fields, ps, alevel, blevel, method="centred", magnitude=None, fdefined_in=None, fdef_ps=SOME_DEFINED, undef=UNDEF,
+                       out=None):
+        """EXTENSION (include/mifc.h, mifc_vderiv_hlevels): the derivative of hybrid-level batches along the coordinate
+        c = alevel[k] + blevel[k] * ps, one value per input level: centred differences ("centred") or the second-order
+        form for uneven spacing ("weighted"), one-sided at the ends and next to holes.  fields, ps, fdefined_in: as
+        vinterp_hlevels takes them.  magnitude: None returns (out (nf, nlev, ny, nx), flags int32 (nf, nlev)); "also"
+        returns (out, flags, mag (nf / 2, nlev, ny, nx), mag_flags (nf / 2, nlev)), mag[j] the magnitude of the derivatives
+        of the fields 2j and 2j + 1; "only" returns (mag, mag_flags) and writes no derivative.  With ONE (nlev, ny, nx)
+        batch for `fields` the leading axis is dropped from out and flags.  out: an array or tensor to write into (with
+        "also": (out, mag)).  A refused call raises RuntimeError."""
+        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
+        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
+        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
+        if al.size != nlev or bl.size != nlev:
+            raise ValueError("alevel and blevel must hold one value per level")
+        return self._vderiv("mifc_vderiv_hlevels", fields, ps, [int(fdef_ps), al, bl], method, magnitude, fdefined_in, undef, out)
+
+    def vderiv_fields(self, fields, coord, method="centred", magnitude=None, fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vderiv_fields): as vderiv_hlevels, the coordinate given as a batch
+        (nlev, ny, nx) like the fields (height, pressure, potential temperature ...); fdef_coord: one flag per level,
+        None: SOME_DEFINED."""
+        fc_ = None
+        if fdef_coord is not None:
+            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
+            if fc_.size != int(_Arg(coord).shape[0]):
+                raise ValueError("fdef_coord must hold one flag per level")
+        return self._vderiv("mifc_vderiv_fields", fields, coord, [fc_], method, magnitude, fdefined_in, undef, out)
+
+    def vderiv_levels(self, fields, levels, method="centred", magnitude=None, fdefined_in=None, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vderiv_levels): as vderiv_hlevels, the coordinate one constant per level
+        (pressure levels, the targets of an earlier vinterp call): `levels` holds nlev numbers."""
+        return self._vderiv("mifc_vderiv_levels", fields, levels, [], method, magnitude, fdefined_in, undef, out)
 
     def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
         """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability

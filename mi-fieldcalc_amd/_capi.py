@@ -129,6 +129,10 @@ SIGNATURES = {
     "mifc_vinterp_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "i", "i", "p", "pi", "f", "i"]),
     "mifc_vlayer_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "f", "f", "p", "p", "pi", "i", "p", "pi", "f", "i"]),
     "mifc_vlayer_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "f", "f", "p", "p", "pi", "i", "p", "pi", "f", "i"]),
+    # EXTENSION: vertical derivatives of level batches (fres, fmag: host tables of pointers, either may be None; levels: host array)
+    "mifc_vderiv_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
+    "mifc_vderiv_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "p", "pi", "p", "pi", "f", "i"]),
+    "mifc_vderiv_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

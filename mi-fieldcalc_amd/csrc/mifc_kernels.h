@@ -379,6 +379,53 @@ struct VlayerParams
 };
 hipError_t launch_vlayer(const VlayerParams& prm, hipStream_t stream);
 
+// ------------------------------------ vertical derivatives of level batches (mifc_vderiv.hip), EXTENSION
+// One launch walks the `nlev` levels of `n` columns once for up to VDERIV_PASS fields and stores, per field and level, the
+// derivative along the coordinate (what & VDERIV_DERIV: out[f] + k * out_stride) and, per pair of fields (2j, 2j + 1)
+// and level, the magnitude of the two derivatives (what & VDERIV_MAG: mag[j] + k * out_stride; nfields is even then).
+// The host launches again for the fields beyond vderiv_pass_fields(what): VDERIV_PASS, or two where both the derivatives
+// and the magnitudes are written (the field counts at which every instance keeps two waves per SIMD without a spill,
+// DESIGN.md 4.17).  Inputs, `coord`, `ab`, `lev_bits` (bit f0 + f = field f of
+// the launch is flagged ALL_DEFINED at level k, bit VINTERP_COORD_BIT = the coordinate is) and vec4 as in VinterpParams.
+// kind VDERIV_LEVELS: the coordinate is one constant per level, nothing is read per cell; the host has put what depends
+// on it into the table: lev_bits bit VDERIV_LOWER_BIT / VDERIV_UPPER_BIT = c_k-1 / c_k+1 exists and differs from c_k,
+// VDERIV_FOLD_BIT = the two-sided denominator is zero; lev_w[4 * k ..] = 1 / (c_k - c_k-1), 1 / (c_k+1 - c_k) and the
+// two-sided weights (CENTRED: w, unused; WEIGHTED: w1, w2).
+// Counters: n_undefined[(f0 + f) * nlev + k], n_undefined_mag[(f0 / 2 + j) * nlev + k], zeroed by the caller; a workgroup
+// gathers its counts in (VDERIV_PASS + VDERIV_PASS / 2) * nlev words of dynamic LDS when lds_counts is set (the launcher
+// sets it where that fits), otherwise a wave adds to the global counters itself.
+const int VDERIV_MAX_FIELDS = 8, VDERIV_PASS = 4, VDERIV_DERIV = 1, VDERIV_MAG = 2;
+const int VDERIV_HYBRID = 0, VDERIV_FIELD = 1, VDERIV_LEVELS = 2;
+const int VDERIV_LOWER_BIT = 9, VDERIV_UPPER_BIT = 10, VDERIV_FOLD_BIT = 11;
+constexpr int vderiv_pass_fields(int what)
+{
+  return what == (VDERIV_DERIV | VDERIV_MAG) ? 2 : VDERIV_PASS;
+}
+struct VderivParams
+{
+  int kind;    // VDERIV_HYBRID / VDERIV_FIELD / VDERIV_LEVELS
+  int what;    // VDERIV_DERIV | VDERIV_MAG
+  int method;  // MIFC_VDERIV_CENTRED / MIFC_VDERIV_WEIGHTED
+  int nfields; // of this launch, 1 .. vderiv_pass_fields(what)
+  int f0;      // the call's field of the launch's field 0 (level bits, counters): even
+  int n;       // columns of this launch
+  int nlev;    // >= 2
+  int vec4;
+  int ps_all;  // hybrid: fdef_ps == ALL_DEFINED
+  int lds_counts; // set by launch_vderiv
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[VDERIV_PASS];
+  float* out[VDERIV_PASS];
+  float* mag[VDERIV_PASS / 2];
+  const float* coord;
+  const float* ab;
+  const unsigned int* lev_bits;
+  const double* lev_w;
+  u64 *n_undefined, *n_undefined_mag;
+};
+hipError_t launch_vderiv(const VderivParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843

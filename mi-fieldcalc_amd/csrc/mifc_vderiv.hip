@@ -1,0 +1,503 @@
+// mifc_vderiv.hip -- vertical derivatives of level batches, with vector magnitude (mifc_vderiv_hlevels / mifc_vderiv_fields /
+// mifc_vderiv_levels, include/mifc.h; EXTENSION: the reference has no function that crosses levels).
+//
+// The walk is the one of mifc_vinterp.hip and mifc_vlayer.hip: consecutive lanes own consecutive cells, four each through
+// 16-byte loads (V = 4) or one each (V = 1), a lane keeps its cells for all levels, three level slots rotate (the k loop
+// unrolled three times so that the slots are static), the per-level scalars come from a small table through the constant
+// address space.  What differs: this kernel writes a full batch.  Output level k needs the levels k - 1, k and k + 1, so
+// it is stored as soon as level k + 1 has arrived; the slots hold k, k + 1 and k + 2 and level k - 1 is carried beside
+// them, so the loads stay two levels ahead of the level being stored, every input level is read once and every output
+// level written once.  A level has two bodies.  Where every cell of the wave has both sides taking part for every field of
+// the launch and no zero denominator -- one ballot -- the fast body runs: the one or two double divisions of the weights
+// per cell, then per field two or three subtractions, multiplications and one addition, no select.  The general body does
+// the rest (the first and the last level, holes, equal or undefined coordinates): it sorts every (field, cell) into
+// both / lower only / upper only / undef, computes only the weights that some cell of the wave needs and selects.  With
+// the coordinate given per level (VDERIV_LEVELS) the weights are the same for every cell: the host has divided, they come
+// in through scalar loads.  Undefined cells are counted per level and field by ballot into LDS and leave the workgroup as
+// one atomic per counter that is not zero.
+#include "mifc_device.h"
+#include "mifc_kernels.h"
+
+#include <type_traits>
+
+namespace mifc {
+
+namespace {
+
+template <int V>
+__device__ __forceinline__ void vd_load(float (&r)[V], const float* p)
+{
+  if constexpr (V == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    r[0] = q.x;
+    r[1] = q.y;
+    r[2] = q.z;
+    r[3] = q.w;
+  } else {
+    r[0] = p[0];
+  }
+}
+
+// the first n_mine cells of a lane (the ones inside the launch): one 16-byte store where that is all four
+template <int V>
+__device__ __forceinline__ void vd_store(float* p, const float (&r)[V], int n_mine)
+{
+  if constexpr (V == 4) {
+    if (n_mine == 4) {
+      *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < V; ++c)
+    if (c < n_mine)
+      p[c] = r[c];
+}
+
+// makes a wave-uniform index opaque to the compiler where it is used (see vl_here in mifc_vlayer.hip)
+__device__ __forceinline__ int vd_here(int uniform)
+{
+  asm volatile("" : "+s"(uniform));
+  return uniform;
+}
+
+// the same for a per-lane word: it is kept in a VGPR instead of being recomputed from lane masks
+__device__ __forceinline__ unsigned int vd_here_v(unsigned int x)
+{
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <int NF, int V>
+struct DerivLevel
+{
+  float c[V]; // field coordinate: as loaded
+  float x[NF][V];
+};
+
+// what a (field, cell) of a level is, two bits: the sides that take part; 0 = the result is undef
+const unsigned int SIDE_LOWER = 1u, SIDE_UPPER = 2u, SIDE_BOTH = 3u;
+// what the coordinate of a cell allows at a level (SIDE_* in the low bits)
+const unsigned int CELL_LOWER = 1u, CELL_UPPER = 2u, CELL_CENTRE = 4u, CELL_FOLD = 8u;
+
+template <int KIND, int W, int NF, int V>
+__global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
+{
+  constexpr int R = 3;       // level slots
+  constexpr int NM = NF / 2; // vectors
+  extern __shared__ unsigned int s_cnt[]; // [NF + NM][nlev]
+  const int nlev = P.nlev, f0 = P.f0;
+  const bool lds = P.lds_counts != 0;
+  const int method = P.method;
+  if (lds) {
+    for (int j = threadIdx.x; j < (NF + NM) * nlev; j += 256)
+      s_cnt[j] = 0;
+    __syncthreads();
+  }
+
+  const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * V;
+  const long left = (long)P.n - i0;
+  const int n_cells = left < 0 ? 0 : (left < V ? (int)left : V); // this lane's cells inside the launch: cells 0 .. n_cells - 1
+  // a wave-uniform base plus the lane's 32-bit byte offset inside the workgroup; lanes past the end walk the workgroup's
+  // first column group and neither store nor count (mifc_vlayer.hip)
+  const long block0 = (long)blockIdx.x * (256 * V);
+  const unsigned int lane_bytes = n_cells > 0 ? threadIdx.x * (unsigned int)(V * sizeof(float)) : 0u;
+  auto lane_of = [&](const float* uniform_base) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(uniform_base) + lane_bytes); };
+  const float undef = P.undef;
+  typedef const __attribute__((address_space(4))) float* ConstFloats;
+  typedef const __attribute__((address_space(4))) unsigned int* ConstWords;
+  typedef const __attribute__((address_space(4))) double* ConstDoubles;
+  const ConstFloats ab = (ConstFloats)(unsigned long long)P.ab;
+  const ConstWords lev_bits = (ConstWords)(unsigned long long)P.lev_bits;
+  const ConstDoubles lev_w = (ConstDoubles)(unsigned long long)P.lev_w;
+  typedef DerivLevel<NF, V> Level;
+
+  auto load = [&](Level& L, int k) {
+    const long off = (long)vd_here(k) * P.in_stride + block0; // (k opaque: no induction variable per pointer)
+    if constexpr (KIND == VDERIV_FIELD)
+      vd_load<V>(L.c, lane_of(P.coord + off));
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      vd_load<V>(L.x[f], lane_of(P.fields[f] + off));
+  };
+
+  // a coordinate that is not usable is carried as NaN (rule 1)
+  const float nan = __int_as_float(0x7fc00000);
+  float ps[V];
+  if constexpr (KIND == VDERIV_HYBRID) {
+    vd_load<V>(ps, lane_of(P.coord + block0));
+#pragma unroll
+    for (int c = 0; c < V; ++c)
+      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan;
+  }
+  auto coordinate = [&](const Level& L, int k, unsigned int bits, float (&cc)[V]) {
+    if constexpr (KIND == VDERIV_HYBRID) {
+      const float a = ab[k], b = ab[nlev + k];
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
+        cc[c] = a + prod;
+      }
+    } else if constexpr (KIND == VDERIV_FIELD) {
+      const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
+#pragma unroll
+      for (int c = 0; c < V; ++c)
+        cc[c] = (all || L.c[c] != undef) ? L.c[c] : nan;
+    } else {
+#pragma unroll
+      for (int c = 0; c < V; ++c)
+        cc[c] = 0.f; // not used: the table says which sides exist
+    }
+  };
+
+  // rule 2 for the values of a level as it arrives: bit f of the cell's word = x_f passes is_defined.  Every value is tested
+  // once; as lane masks the tests of the three levels in flight would not fit into the SGPRs
+  auto defined = [&](const Level& L, unsigned int bits, unsigned int (&df)[V]) {
+    const unsigned int all = bits >> f0;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+      unsigned int w = 0;
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+        w |= (((all >> f) & 1u) != 0 || is_def(L.x[f][c], undef)) ? 1u << f : 0u;
+      df[c] = vd_here_v(w);
+    }
+  };
+
+  auto count = [&](int slot, int k, unsigned int n) {
+    // (the lane test and the row of the counter computed here, not kept in SGPRs through the walk)
+    if (n != 0 && (vd_here_v(threadIdx.x) & 63) == 0) {
+      const int row = vd_here(nlev), first = vd_here(f0);
+      if (lds)
+        atomicAdd(&s_cnt[slot * row + k], n);
+      else if (slot < NF)
+        atomicAdd(P.n_undefined + (long)(first + slot) * row + k, (u64)n);
+      else
+        atomicAdd(P.n_undefined_mag + (long)(first / 2 + slot - NF) * row + k, (u64)n);
+    }
+  };
+
+  // stores level k: the derivatives and / or the magnitudes; FAST: nothing is undef, nothing to count
+  auto emit = [&](auto fast, const float (&res)[NF][V], const unsigned int (&cls)[V], int k) {
+    constexpr bool FAST = decltype(fast)::value;
+    const long at = (long)vd_here(k) * P.out_stride + i0;
+    const int n_mine = (int)vd_here_v((unsigned int)n_cells); // (compared here: no lane masks that live through the walk)
+    if constexpr ((W & VDERIV_DERIV) != 0) {
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        if constexpr (!FAST) {
+          unsigned int n = 0;
+#pragma unroll
+          for (int c = 0; c < V; ++c)
+            n += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(((cls[c] >> (2 * f)) & 3u) == 0 && c < n_mine));
+          count(f, k, n);
+        }
+        vd_store<V>(P.out[vd_here(f)] + at, res[f], n_mine);
+      }
+    }
+    if constexpr ((W & VDERIV_MAG) != 0) {
+#pragma unroll
+      for (int j = 0; j < NM; ++j) {
+        float m[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+          m[c] = absval(res[2 * j][c], res[2 * j + 1][c]); // rule 8
+        if constexpr (!FAST) {
+          unsigned int n = 0;
+#pragma unroll
+          for (int c = 0; c < V; ++c) {
+            const bool bad = ((cls[c] >> (4 * j)) & 3u) == 0 || ((cls[c] >> (4 * j + 2)) & 3u) == 0;
+            m[c] = bad ? undef : m[c];
+            n += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(bad && c < n_mine));
+          }
+          count(NF + j, k, n);
+        }
+        vd_store<V>(P.mag[vd_here(j)] + at, m, n_mine);
+      }
+    }
+  };
+
+  // Output level k from the levels k - 1 (lo), k (cur) and k + 1 (hi) and their coordinates cp, cc, cn.
+  // dfp, dfk, dfn: the words of defined() for the three levels.
+  auto level = [&](const Level& lo, const Level& cur, const Level& hi, const float (&cp)[V], const float (&cc)[V], const float (&cn)[V],
+                   const unsigned int (&dfp)[V], const unsigned int (&dfk)[V], const unsigned int (&dfn)[V], unsigned int bits_k, int k) {
+    // rules 1 and 3 for the coordinate: is c_k usable, does c_k-1 / c_k+1 exist, is it usable and different
+    // per cell in a VGPR (as lane masks these sixteen tests would take more SGPRs than a wave has to spare): CELL_LOWER /
+    // CELL_UPPER = the side's coordinate is usable and differs, CELL_CENTRE = c_k is usable, CELL_FOLD = zero denominator
+    const bool weighted = vd_here(method) != 0; // (tested here: as lane masks for the selects it would sit in four SGPRs through the walk)
+    unsigned int cm[V];
+    double h1[V], h2[V], den[V];
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+      if constexpr (KIND == VDERIV_LEVELS) {
+        cm[c] = ((bits_k >> VDERIV_LOWER_BIT) & 1u) * CELL_LOWER | ((bits_k >> VDERIV_UPPER_BIT) & 1u) * CELL_UPPER | CELL_CENTRE |
+                ((bits_k >> VDERIV_FOLD_BIT) & 1u) * CELL_FOLD;
+        h1[c] = h2[c] = den[c] = 0.0;
+      } else {
+        const double dm = (double)cp[c], d0 = (double)cc[c], dp = (double)cn[c];
+        h1[c] = d0 - dm;
+        h2[c] = dp - d0;
+        const double s = h1[c] + h2[c], dc = dp - dm;
+        den[c] = weighted ? s : dc;
+        cm[c] = ((cp[c] == cp[c] && cp[c] != cc[c]) ? CELL_LOWER : 0u) | // (no level k - 1: cp is NaN)
+                ((cn[c] == cn[c] && cn[c] != cc[c]) ? CELL_UPPER : 0u) | (cc[c] == cc[c] ? CELL_CENTRE : 0u) | (den[c] == 0.0 ? CELL_FOLD : 0u);
+        cm[c] = vd_here_v(cm[c]);
+      }
+    }
+    // the two-sided weights of rule 4 (CENTRED: wa = w; WEIGHTED: wa = w1, wb = w2)
+    auto both_weights = [&](double (&wa)[V], double (&wb)[V]) {
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        if constexpr (KIND == VDERIV_LEVELS) {
+          wa[c] = lev_w[4 * k + 2];
+          wb[c] = lev_w[4 * k + 3];
+        } else if (weighted) {
+          const double p1 = h1[c] * den[c], p2 = h2[c] * den[c];
+          wa[c] = h2[c] / p1;
+          wb[c] = h1[c] / p2;
+        } else {
+          wa[c] = 1.0 / den[c];
+          wb[c] = 0.0;
+        }
+      }
+    };
+
+    unsigned int cls[V];
+    unsigned int every = SIDE_BOTH; // the AND of the lane's classes: SIDE_BOTH = all of them are
+    unsigned int any = 0;           // which classes this lane has: bit s - 1 for SIDE_* s
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+      cls[c] = 0;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const unsigned int okbits = ((dfp[c] >> f) & 1u) * CELL_LOWER | ((dfn[c] >> f) & 1u) * CELL_UPPER | ((dfk[c] >> f) & 1u) * CELL_CENTRE | CELL_FOLD;
+        const unsigned int t = cm[c] & okbits;
+        unsigned int s = t & SIDE_BOTH; // rule 3 (CELL_LOWER, CELL_UPPER are SIDE_LOWER, SIDE_UPPER)
+        s = ((t & CELL_CENTRE) != 0 && t != (SIDE_BOTH | CELL_CENTRE | CELL_FOLD)) ? s : 0u; // rule 2; rule 4's zero denominator
+        cls[c] |= s << (2 * f);
+        any |= (1u << s) >> 1;
+        every &= s;
+      }
+    }
+    const bool good = every == SIDE_BOTH;
+
+    float res[NF][V];
+    if (__builtin_amdgcn_ballot_w64(!good) == 0) {
+      // the fast body: both sides everywhere in the wave
+      double wa[V], wb[V];
+      both_weights(wa, wb);
+      if (weighted) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+          for (int c = 0; c < V; ++c) {
+            const double xm = (double)lo.x[f][c], x0 = (double)cur.x[f][c], xp = (double)hi.x[f][c];
+            const double d1 = x0 - xm, d2 = xp - x0;
+            const double t1 = d1 * wa[c], t2 = d2 * wb[c];
+            const double r = t1 + t2;
+            res[f][c] = (float)r;
+          }
+      } else {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+          for (int c = 0; c < V; ++c) {
+            const double d = (double)hi.x[f][c] - (double)lo.x[f][c];
+            const double r = d * wa[c];
+            res[f][c] = (float)r;
+          }
+      }
+      emit(std::true_type(), res, cls, k);
+      return;
+    }
+
+    // the general body: only the weights that some cell of the wave needs
+    double wl[V], wh[V], wa[V], wb[V];
+#pragma unroll
+    for (int c = 0; c < V; ++c)
+      wl[c] = wh[c] = wa[c] = wb[c] = 0.0;
+    if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_LOWER - 1))) != 0) != 0) {
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        if constexpr (KIND == VDERIV_LEVELS)
+          wl[c] = lev_w[4 * k];
+        else
+          wl[c] = 1.0 / h1[c];
+      }
+    }
+    if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_UPPER - 1))) != 0) != 0) {
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        if constexpr (KIND == VDERIV_LEVELS)
+          wh[c] = lev_w[4 * k + 1];
+        else
+          wh[c] = 1.0 / h2[c];
+      }
+    }
+    if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_BOTH - 1))) != 0) != 0)
+      both_weights(wa, wb);
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const unsigned int s = (cls[c] >> (2 * f)) & 3u;
+        const double xm = (double)lo.x[f][c], x0 = (double)cur.x[f][c], xp = (double)hi.x[f][c];
+        const double d1 = x0 - xm, d2 = xp - x0, d = xp - xm;
+        const double one_lower = d1 * wl[c], one_upper = d2 * wh[c]; // rule 5
+        const double t1 = d1 * wa[c], t2 = d2 * wb[c];
+        const double sum = t1 + t2, centred = d * wa[c];
+        const double both = weighted ? sum : centred;
+        const double r = s == SIDE_BOTH ? both : (s == SIDE_LOWER ? one_lower : one_upper);
+        res[f][c] = s == 0 ? undef : (float)r;
+      }
+    emit(std::false_type(), res, cls, k);
+  };
+
+  Level L[R], prev;
+#pragma unroll
+  for (int c = 0; c < V; ++c) {
+    prev.c[c] = L[2].c[c] = 0.f;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      prev.x[f][c] = L[2].x[f][c] = 0.f;
+  }
+  load(L[0], 0);
+  load(L[1], 1);
+  if (2 < nlev)
+    load(L[2], 2);
+
+  unsigned int bits_k = lev_bits[0];
+  float cp[V], cc[V];
+  unsigned int dfp[V], dfk[V];
+#pragma unroll
+  for (int c = 0; c < V; ++c) {
+    cp[c] = nan;
+    dfp[c] = 0;
+  }
+  coordinate(L[0], 0, bits_k, cc);
+  defined(L[0], bits_k, dfk);
+
+  for (int k0 = 0; k0 < nlev; k0 += R) {
+#pragma unroll
+    for (int d = 0; d < R; ++d) {
+      const int k = k0 + d; // the output level
+      if (k < nlev) {
+        Level& cur = L[d];
+        Level& nx = L[(d + 1) % R];
+        const bool has_next = k + 1 < nlev;
+        const unsigned int bits_n = lev_bits[has_next ? k + 1 : k];
+        float cn[V];
+        coordinate(nx, has_next ? k + 1 : k, bits_n, cn);
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+          cn[c] = has_next ? cn[c] : nan;
+        unsigned int dfn[V];
+        defined(nx, bits_n, dfn); // (no level k + 1: cn is NaN)
+        level(prev, cur, nx, cp, cc, cn, dfp, dfk, dfn, bits_k, k);
+        // level k becomes level k - 1, level k + 1 level k; level k's slot takes level k + 3
+        prev = cur;
+        bits_k = bits_n;
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          cp[c] = cc[c];
+          cc[c] = cn[c];
+          dfp[c] = dfk[c];
+          dfk[c] = dfn[c];
+        }
+        if (k + R < nlev)
+          load(cur, k + R);
+      }
+    }
+  }
+
+  if (lds) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < (NF + NM) * nlev; j += 256) {
+      const unsigned int n = s_cnt[j];
+      if (n != 0) {
+        const int slot = j / nlev, k = j - slot * nlev;
+        if (slot < NF)
+          atomicAdd(P.n_undefined + (long)(f0 + slot) * nlev + k, (u64)n);
+        else
+          atomicAdd(P.n_undefined_mag + (long)(f0 / 2 + slot - NF) * nlev + k, (u64)n);
+      }
+    }
+  }
+}
+
+template <int KIND, int W, int NF>
+hipError_t launch_v(const VderivParams& P, hipStream_t stream)
+{
+  const int per_block = 256 * (P.vec4 ? 4 : 1);
+  const dim3 grid((unsigned int)(((long)P.n + per_block - 1) / per_block)), block(256);
+  const size_t lds = P.lds_counts ? (size_t)(NF + NF / 2) * (size_t)P.nlev * sizeof(unsigned int) : 0;
+  if (P.vec4)
+    hipLaunchKernelGGL((vderiv_kernel<KIND, W, NF, 4>), grid, block, lds, stream, P);
+  else
+    hipLaunchKernelGGL((vderiv_kernel<KIND, W, NF, 1>), grid, block, lds, stream, P);
+  return hipGetLastError();
+}
+
+template <int KIND, int W>
+hipError_t launch_nf(const VderivParams& P, hipStream_t stream)
+{
+  static_assert(VDERIV_PASS == 4, "one case per field count of a launch");
+  switch (P.nfields) {
+  case 1:
+    if constexpr ((W & VDERIV_MAG) == 0)
+      return launch_v<KIND, W, 1>(P, stream);
+    return hipErrorInvalidValue; // (a magnitude takes a pair)
+  case 2:
+    return launch_v<KIND, W, 2>(P, stream);
+  case 3:
+    if constexpr ((W & VDERIV_MAG) == 0)
+      return launch_v<KIND, W, 3>(P, stream);
+    return hipErrorInvalidValue;
+  case 4:
+    if constexpr (vderiv_pass_fields(W) >= 4)
+      return launch_v<KIND, W, 4>(P, stream);
+    return hipErrorInvalidValue; // (the instances beyond a launch's capacity do not exist)
+  default:
+    return hipErrorInvalidValue;
+  }
+}
+
+template <int KIND>
+hipError_t launch_what(const VderivParams& P, hipStream_t stream)
+{
+  switch (P.what) {
+  case VDERIV_DERIV:
+    return launch_nf<KIND, VDERIV_DERIV>(P, stream);
+  case VDERIV_MAG:
+    return launch_nf<KIND, VDERIV_MAG>(P, stream);
+  case VDERIV_DERIV | VDERIV_MAG:
+    return launch_nf<KIND, VDERIV_DERIV | VDERIV_MAG>(P, stream);
+  default:
+    return hipErrorInvalidValue;
+  }
+}
+
+} // namespace
+
+hipError_t launch_vderiv(const VderivParams& prm, hipStream_t stream)
+{
+  if (prm.n <= 0)
+    return hipSuccess;
+  if (prm.nlev < 2 || prm.f0 < 0 || (prm.f0 & 1) != 0 || prm.f0 + prm.nfields > VDERIV_MAX_FIELDS)
+    return hipErrorInvalidValue;
+  VderivParams P = prm;
+  // the workgroup's counters in LDS where they fit into half of what two resident workgroups may share
+  P.lds_counts = (size_t)(VDERIV_PASS + VDERIV_PASS / 2) * (size_t)P.nlev * sizeof(unsigned int) <= 32768 ? 1 : 0;
+  switch (P.kind) {
+  case VDERIV_HYBRID:
+    return launch_what<VDERIV_HYBRID>(P, stream);
+  case VDERIV_FIELD:
+    return launch_what<VDERIV_FIELD>(P, stream);
+  case VDERIV_LEVELS:
+    return launch_what<VDERIV_LEVELS>(P, stream);
+  default:
+    return hipErrorInvalidValue;
+  }
+}
+
+} // namespace mifc
