@@ -174,6 +174,65 @@ def _empty_like(ref, shape=None):
     return np.empty(shape or np.shape(ref), dtype=np.float32)
 
 
+# ------------------------------------------------ what the level-batch methods (vinterp, vlayer, vderiv) take alike
+def _level_batches(fields):
+    """One (nlev, ny, nx) batch, a stacked (nf, nlev, ny, nx) array / tensor or a sequence of batches: (was it one, the
+    batches, their _Arg, the shape of a batch)."""
+    one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
+    if one:
+        batches = [fields]
+    elif isinstance(fields, np.ndarray) or _is_torch(fields):
+        batches = [fields[f] for f in range(fields.shape[0])]
+    else:
+        batches = list(fields)
+    if not batches:
+        raise ValueError("no fields")
+    fa = [_Arg(b) for b in batches]
+    shape = tuple(fa[0].shape)
+    if len(shape) != 3:
+        raise ValueError("fields must be (nlev, ny, nx) batches")
+    if not _same_shape(fa, shape):
+        raise ValueError("every field must have the shape %s" % (shape,))
+    return one, batches, fa, shape
+
+
+def _level_coord(coord, hybrid, shape):
+    """The coordinate argument: ps (ny, nx) of the hybrid form, else a batch like the fields."""
+    ca = _Arg(coord)
+    want = shape[1:] if hybrid else shape
+    if tuple(ca.shape) != want:
+        raise ValueError("the coordinate must have the shape %s" % (want,))
+    return ca
+
+
+def _level_flags(fdefined_in, nf, nlev):
+    """fdefined_in as the (nf, nlev) table the C entries take, None as it is."""
+    if fdefined_in is None:
+        return None
+    f = np.asarray(fdefined_in, dtype=np.int32)
+    if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
+        f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
+    return np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+
+
+def _hybrid_levels(fields, alevel, blevel):
+    al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
+    bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
+    nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
+    if al.size != nlev or bl.size != nlev:
+        raise ValueError("alevel and blevel must hold one value per level")
+    return al, bl
+
+
+def _coord_flags(fdef_coord, coord):
+    if fdef_coord is None:
+        return None
+    fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
+    if fc_.size != int(_Arg(coord).shape[0]):
+        raise ValueError("fdef_coord must hold one flag per level")
+    return fc_
+
+
 class Context:
     """One mifc_ctx: a HIP device, a stream, staging scratch.  Not thread-safe;
     create one per thread (the reference is re-entrant)."""
@@ -636,26 +695,9 @@ class Context:
     # ------------------------------------------------------ level batches to constant surfaces (EXTENSION)
     def _vinterp(self, name, fields, coord, coord_args, targets, method, fdefined_in, undef, out):
         code = {"linear": 0, "log": 1}.get(method, -1) if isinstance(method, str) else int(method)
-        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
-        if one:
-            batches = [fields]
-        elif isinstance(fields, np.ndarray) or _is_torch(fields):
-            batches = [fields[f] for f in range(fields.shape[0])]
-        else:
-            batches = list(fields)
-        if not batches:
-            raise ValueError("no fields")
-        fa = [_Arg(b) for b in batches]
-        shape = tuple(fa[0].shape)
-        if len(shape) != 3:
-            raise ValueError("fields must be (nlev, ny, nx) batches")
-        if not _same_shape(fa, shape):
-            raise ValueError("every field must have the shape %s" % (shape,))
+        one, batches, fa, shape = _level_batches(fields)
         nlev, ny, nx = shape
-        ca = _Arg(coord)
-        want = (ny, nx) if name == "mifc_vinterp_hlevels" else shape
-        if tuple(ca.shape) != want:
-            raise ValueError("the coordinate must have the shape %s" % (want,))
+        ca = _level_coord(coord, name == "mifc_vinterp_hlevels", shape)
         tg = np.ascontiguousarray(np.asarray(targets, dtype=np.float32).ravel())
         nt, nf = int(tg.size), len(fa)
         out_shape = (nt, ny, nx) if one else (nf, nt, ny, nx)
@@ -668,12 +710,7 @@ class Context:
         self._bind_stream(mk)
         table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
         outs = (ctypes.c_void_p * nf)(*[oa.addr + f * nt * ny * nx * 4 for f in range(nf)])
-        flags = None
-        if fdefined_in is not None:
-            f = np.asarray(fdefined_in, dtype=np.int32)
-            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
-                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
-            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        flags = _level_flags(fdefined_in, nf, nlev)
         fd = np.zeros((nf, nt), np.int32)
         args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, ca.addr] + coord_args + [tg, nt, code, ctypes.addressof(outs), fd, float(undef), mk]
         if not self._call(name, args):
@@ -688,47 +725,22 @@ class Context:
         or CUDA tensors (device), or one stacked (nf, nlev, ny, nx); ps: (ny, nx); fdefined_in: flags (nf, nlev), or one
         per field; None: SOME_DEFINED.  Returns (out (nf, ntargets, ny, nx), flags int32 (nf, ntargets)); with ONE
         (nlev, ny, nx) batch for `fields` the leading axis is dropped from both.  A refused call raises RuntimeError."""
-        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
-        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
-        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
-        if al.size != nlev or bl.size != nlev:
-            raise ValueError("alevel and blevel must hold one value per level")
+        al, bl = _hybrid_levels(fields, alevel, blevel)
         return self._vinterp("mifc_vinterp_hlevels", fields, ps, [int(fdef_ps), al, bl], targets, method, fdefined_in, undef, out)
 
     def vinterp_fields(self, fields, coord, targets, method="linear", fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
         """EXTENSION (include/mifc.h, mifc_vinterp_fields): as vinterp_hlevels, the coordinate given as a batch
         (nlev, ny, nx) like the fields (pressure on other level types, height, potential temperature ...);
         fdef_coord: one flag per level, None: SOME_DEFINED."""
-        fc_ = None
-        if fdef_coord is not None:
-            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
-            if fc_.size != int(_Arg(coord).shape[0]):
-                raise ValueError("fdef_coord must hold one flag per level")
+        fc_ = _coord_flags(fdef_coord, coord)
         return self._vinterp("mifc_vinterp_fields", fields, coord, [fc_], targets, method, fdefined_in, undef, out)
 
     # ------------------------------------------ layer integrals, means and extremes of level batches (EXTENSION)
     def _vlayer(self, name, fields, coord, coord_args, products, lo, hi, fdefined_in, undef, out):
         codes = [VLAYER_PRODUCTS.get(p, -1) if isinstance(p, str) else int(p) for p in ([products] if isinstance(products, (str, int)) else products)]
-        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
-        if one:
-            batches = [fields]
-        elif isinstance(fields, np.ndarray) or _is_torch(fields):
-            batches = [fields[f] for f in range(fields.shape[0])]
-        else:
-            batches = list(fields)
-        if not batches:
-            raise ValueError("no fields")
-        fa = [_Arg(b) for b in batches]
-        shape = tuple(fa[0].shape)
-        if len(shape) != 3:
-            raise ValueError("fields must be (nlev, ny, nx) batches")
-        if not _same_shape(fa, shape):
-            raise ValueError("every field must have the shape %s" % (shape,))
+        one, batches, fa, shape = _level_batches(fields)
         nlev, ny, nx = shape
-        ca = _Arg(coord)
-        want = (ny, nx) if name == "mifc_vlayer_hlevels" else shape
-        if tuple(ca.shape) != want:
-            raise ValueError("the coordinate must have the shape %s" % (want,))
+        ca = _level_coord(coord, name == "mifc_vlayer_hlevels", shape)
         bounds, scalars, ptrs = [], [], []
         for b in (lo, hi):  # a number, or a (ny, nx) field of per-cell bounds
             if (isinstance(b, np.ndarray) and b.ndim > 0) or _is_torch(b):
@@ -752,12 +764,7 @@ class Context:
         self._bind_stream(mk)
         table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
         outs = (ctypes.c_void_p * nf)(*[oa.addr + f * np_ * ny * nx * 4 for f in range(nf)])
-        flags = None
-        if fdefined_in is not None:
-            f = np.asarray(fdefined_in, dtype=np.int32)
-            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
-                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
-            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        flags = _level_flags(fdefined_in, nf, nlev)
         pc = np.ascontiguousarray(codes, dtype=np.int32)
         fd = np.zeros((nf, np_), np.int32)
         args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, ca.addr] + coord_args + scalars + ptrs + [pc, np_, ctypes.addressof(outs), fd, float(undef), mk]
@@ -775,21 +782,13 @@ class Context:
         (ny, nx) array / tensor of per-cell bounds.  Returns (out (nf, nproducts, ny, nx), flags int32
         (nf, nproducts)); with ONE (nlev, ny, nx) batch for `fields` the leading axis is dropped from both.  A refused
         call raises RuntimeError."""
-        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
-        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
-        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
-        if al.size != nlev or bl.size != nlev:
-            raise ValueError("alevel and blevel must hold one value per level")
+        al, bl = _hybrid_levels(fields, alevel, blevel)
         return self._vlayer("mifc_vlayer_hlevels", fields, ps, [int(fdef_ps), al, bl], products, lo, hi, fdefined_in, undef, out)
 
     def vlayer_fields(self, fields, coord, products, lo=-np.inf, hi=np.inf, fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
         """EXTENSION (include/mifc.h, mifc_vlayer_fields): as vlayer_hlevels, the coordinate given as a batch
         (nlev, ny, nx) like the fields; fdef_coord: one flag per level, None: SOME_DEFINED."""
-        fc_ = None
-        if fdef_coord is not None:
-            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
-            if fc_.size != int(_Arg(coord).shape[0]):
-                raise ValueError("fdef_coord must hold one flag per level")
+        fc_ = _coord_flags(fdef_coord, coord)
         return self._vlayer("mifc_vlayer_fields", fields, coord, [fc_], products, lo, hi, fdefined_in, undef, out)
 
     # ------------------------------------------ vertical derivatives of level batches, vector magnitude (EXTENSION)
@@ -797,21 +796,7 @@ class Context:
         code = VDERIV_METHODS.get(method, -1) if isinstance(method, str) else int(method)
         if magnitude not in (None, "also", "only"):
             raise ValueError('magnitude must be None, "also" or "only"')
-        one = (isinstance(fields, np.ndarray) or _is_torch(fields)) and len(fields.shape) == 3
-        if one:
-            batches = [fields]
-        elif isinstance(fields, np.ndarray) or _is_torch(fields):
-            batches = [fields[f] for f in range(fields.shape[0])]
-        else:
-            batches = list(fields)
-        if not batches:
-            raise ValueError("no fields")
-        fa = [_Arg(b) for b in batches]
-        shape = tuple(fa[0].shape)
-        if len(shape) != 3:
-            raise ValueError("fields must be (nlev, ny, nx) batches")
-        if not _same_shape(fa, shape):
-            raise ValueError("every field must have the shape %s" % (shape,))
+        one, batches, fa, shape = _level_batches(fields)
         nlev, ny, nx = shape
         nf = len(fa)
         nm = nf // 2
@@ -822,10 +807,7 @@ class Context:
                 raise ValueError("levels must hold one value per level")
             coord_arg = lv
         else:
-            ca = _Arg(coord)
-            want = (ny, nx) if name == "mifc_vderiv_hlevels" else shape
-            if tuple(ca.shape) != want:
-                raise ValueError("the coordinate must have the shape %s" % (want,))
+            ca = _level_coord(coord, name == "mifc_vderiv_hlevels", shape)
             coord_arg = ca.addr
             others.append(ca)
         want_out, want_mag = magnitude != "only", magnitude is not None
@@ -854,12 +836,7 @@ class Context:
         if want_mag:
             mags = (ctypes.c_void_p * max(nm, 1))(*[res[-1][1].addr + j * batch_bytes for j in range(nm)])
             mfd = np.zeros((nm, nlev), np.int32)
-        flags = None
-        if fdefined_in is not None:
-            f = np.asarray(fdefined_in, dtype=np.int32)
-            if f.size == nf:  # one flag per field stands for every level (nlev >= 2: never mistaken for the full table)
-                f = np.repeat(f.reshape(nf, 1), nlev, axis=1)
-            flags = np.ascontiguousarray(f.reshape(nf, nlev), dtype=np.int32)
+        flags = _level_flags(fdefined_in, nf, nlev)
         args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, coord_arg] + coord_args + [
             code, ctypes.addressof(outs) if want_out else None, fd, ctypes.addressof(mags) if want_mag else None, mfd, float(undef), mk]
         if not self._call(name, args):
@@ -881,22 +858,14 @@ class Context:
         of the fields 2j and 2j + 1; "only" returns (mag, mag_flags) and writes no derivative.  With ONE (nlev, ny, nx)
         batch for `fields` the leading axis is dropped from out and flags.  out: an array or tensor to write into (with
         "also": (out, mag)).  A refused call raises RuntimeError."""
-        al = np.ascontiguousarray(np.asarray(alevel, dtype=np.float32).ravel())
-        bl = np.ascontiguousarray(np.asarray(blevel, dtype=np.float32).ravel())
-        nlev = int(fields[0].shape[-3]) if not hasattr(fields, "shape") else int(fields.shape[-3])
-        if al.size != nlev or bl.size != nlev:
-            raise ValueError("alevel and blevel must hold one value per level")
+        al, bl = _hybrid_levels(fields, alevel, blevel)
         return self._vderiv("mifc_vderiv_hlevels", fields, ps, [int(fdef_ps), al, bl], method, magnitude, fdefined_in, undef, out)
 
     def vderiv_fields(self, fields, coord, method="centred", magnitude=None, fdefined_in=None, fdef_coord=None, undef=UNDEF, out=None):
         """EXTENSION (include/mifc.h, mifc_vderiv_fields): as vderiv_hlevels, the coordinate given as a batch
         (nlev, ny, nx) like the fields (height, pressure, potential temperature ...); fdef_coord: one flag per level,
         None: SOME_DEFINED."""
-        fc_ = None
-        if fdef_coord is not None:
-            fc_ = np.ascontiguousarray(np.asarray(fdef_coord, dtype=np.int32).ravel())
-            if fc_.size != int(_Arg(coord).shape[0]):
-                raise ValueError("fdef_coord must hold one flag per level")
+        fc_ = _coord_flags(fdef_coord, coord)
         return self._vderiv("mifc_vderiv_fields", fields, coord, [fc_], method, magnitude, fdefined_in, undef, out)
 
     def vderiv_levels(self, fields, levels, method="centred", magnitude=None, fdefined_in=None, undef=UNDEF, out=None):

@@ -15,6 +15,7 @@
 // the coordinate given per level (VDERIV_LEVELS) the weights are the same for every cell: the host has divided, they come
 // in through scalar loads.  Undefined cells are counted per level and field by ballot into LDS and leave the workgroup as
 // one atomic per counter that is not zero.
+#include "mifc_column_walk.h"
 #include "mifc_device.h"
 #include "mifc_kernels.h"
 
@@ -23,57 +24,6 @@
 namespace mifc {
 
 namespace {
-
-template <int V>
-__device__ __forceinline__ void vd_load(float (&r)[V], const float* p)
-{
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x;
-    r[1] = q.y;
-    r[2] = q.z;
-    r[3] = q.w;
-  } else {
-    r[0] = p[0];
-  }
-}
-
-// the first n_mine cells of a lane (the ones inside the launch): one 16-byte store where that is all four
-template <int V>
-__device__ __forceinline__ void vd_store(float* p, const float (&r)[V], int n_mine)
-{
-  if constexpr (V == 4) {
-    if (n_mine == 4) {
-      *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < V; ++c)
-    if (c < n_mine)
-      p[c] = r[c];
-}
-
-// makes a wave-uniform index opaque to the compiler where it is used (see vl_here in mifc_vlayer.hip)
-__device__ __forceinline__ int vd_here(int uniform)
-{
-  asm volatile("" : "+s"(uniform));
-  return uniform;
-}
-
-// the same for a per-lane word: it is kept in a VGPR instead of being recomputed from lane masks
-__device__ __forceinline__ unsigned int vd_here_v(unsigned int x)
-{
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-template <int NF, int V>
-struct DerivLevel
-{
-  float c[V]; // field coordinate: as loaded
-  float x[NF][V];
-};
 
 // what a (field, cell) of a level is, two bits: the sides that take part; 0 = the result is undef
 const unsigned int SIDE_LOWER = 1u, SIDE_UPPER = 2u, SIDE_BOTH = 3u;
@@ -104,28 +54,25 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
   const unsigned int lane_bytes = n_cells > 0 ? threadIdx.x * (unsigned int)(V * sizeof(float)) : 0u;
   auto lane_of = [&](const float* uniform_base) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(uniform_base) + lane_bytes); };
   const float undef = P.undef;
-  typedef const __attribute__((address_space(4))) float* ConstFloats;
-  typedef const __attribute__((address_space(4))) unsigned int* ConstWords;
-  typedef const __attribute__((address_space(4))) double* ConstDoubles;
   const ConstFloats ab = (ConstFloats)(unsigned long long)P.ab;
   const ConstWords lev_bits = (ConstWords)(unsigned long long)P.lev_bits;
   const ConstDoubles lev_w = (ConstDoubles)(unsigned long long)P.lev_w;
-  typedef DerivLevel<NF, V> Level;
+  typedef WalkLevel<NF, V> Level;
 
   auto load = [&](Level& L, int k) {
-    const long off = (long)vd_here(k) * P.in_stride + block0; // (k opaque: no induction variable per pointer)
+    const long off = (long)walk_here(k) * P.in_stride + block0; // (k opaque: no induction variable per pointer)
     if constexpr (KIND == VDERIV_FIELD)
-      vd_load<V>(L.c, lane_of(P.coord + off));
+      walk_load<V>(L.c, lane_of(P.coord + off));
 #pragma unroll
     for (int f = 0; f < NF; ++f)
-      vd_load<V>(L.x[f], lane_of(P.fields[f] + off));
+      walk_load<V>(L.x[f], lane_of(P.fields[f] + off));
   };
 
   // a coordinate that is not usable is carried as NaN (rule 1)
   const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (KIND == VDERIV_HYBRID) {
-    vd_load<V>(ps, lane_of(P.coord + block0));
+    walk_load<V>(ps, lane_of(P.coord + block0));
 #pragma unroll
     for (int c = 0; c < V; ++c)
       ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan;
@@ -160,14 +107,14 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
 #pragma unroll
       for (int f = 0; f < NF; ++f)
         w |= (((all >> f) & 1u) != 0 || is_def(L.x[f][c], undef)) ? 1u << f : 0u;
-      df[c] = vd_here_v(w);
+      df[c] = walk_here_v(w);
     }
   };
 
   auto count = [&](int slot, int k, unsigned int n) {
     // (the lane test and the row of the counter computed here, not kept in SGPRs through the walk)
-    if (n != 0 && (vd_here_v(threadIdx.x) & 63) == 0) {
-      const int row = vd_here(nlev), first = vd_here(f0);
+    if (n != 0 && (walk_here_v(threadIdx.x) & 63) == 0) {
+      const int row = walk_here(nlev), first = walk_here(f0);
       if (lds)
         atomicAdd(&s_cnt[slot * row + k], n);
       else if (slot < NF)
@@ -180,8 +127,8 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
   // stores level k: the derivatives and / or the magnitudes; FAST: nothing is undef, nothing to count
   auto emit = [&](auto fast, const float (&res)[NF][V], const unsigned int (&cls)[V], int k) {
     constexpr bool FAST = decltype(fast)::value;
-    const long at = (long)vd_here(k) * P.out_stride + i0;
-    const int n_mine = (int)vd_here_v((unsigned int)n_cells); // (compared here: no lane masks that live through the walk)
+    const long at = (long)walk_here(k) * P.out_stride + i0;
+    const int n_mine = (int)walk_here_v((unsigned int)n_cells); // (compared here: no lane masks that live through the walk)
     if constexpr ((W & VDERIV_DERIV) != 0) {
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
@@ -192,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
             n += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(((cls[c] >> (2 * f)) & 3u) == 0 && c < n_mine));
           count(f, k, n);
         }
-        vd_store<V>(P.out[vd_here(f)] + at, res[f], n_mine);
+        walk_store<V>(P.out[walk_here(f)] + at, res[f], n_mine);
       }
     }
     if constexpr ((W & VDERIV_MAG) != 0) {
@@ -212,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
           }
           count(NF + j, k, n);
         }
-        vd_store<V>(P.mag[vd_here(j)] + at, m, n_mine);
+        walk_store<V>(P.mag[walk_here(j)] + at, m, n_mine);
       }
     }
   };
@@ -224,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
     // rules 1 and 3 for the coordinate: is c_k usable, does c_k-1 / c_k+1 exist, is it usable and different
     // per cell in a VGPR (as lane masks these sixteen tests would take more SGPRs than a wave has to spare): CELL_LOWER /
     // CELL_UPPER = the side's coordinate is usable and differs, CELL_CENTRE = c_k is usable, CELL_FOLD = zero denominator
-    const bool weighted = vd_here(method) != 0; // (tested here: as lane masks for the selects it would sit in four SGPRs through the walk)
+    const bool weighted = walk_here(method) != 0; // (tested here: as lane masks for the selects it would sit in four SGPRs through the walk)
     unsigned int cm[V];
     double h1[V], h2[V], den[V];
 #pragma unroll
@@ -241,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
         den[c] = weighted ? s : dc;
         cm[c] = ((cp[c] == cp[c] && cp[c] != cc[c]) ? CELL_LOWER : 0u) | // (no level k - 1: cp is NaN)
                 ((cn[c] == cn[c] && cn[c] != cc[c]) ? CELL_UPPER : 0u) | (cc[c] == cc[c] ? CELL_CENTRE : 0u) | (den[c] == 0.0 ? CELL_FOLD : 0u);
-        cm[c] = vd_here_v(cm[c]);
+        cm[c] = walk_here_v(cm[c]);
       }
     }
     // the two-sided weights of rule 4 (CENTRED: wa = w; WEIGHTED: wa = w1, wb = w2)

@@ -12,26 +12,13 @@
 // results are stored straight away; LOG takes its two log() only there, log(ct) comes from the host.  Targets never
 // found are stored as undef behind the walk.  Undefined results are counted per wave by ballot into a table in LDS and
 // leave the workgroup as one atomic per (field, target) that has something to count.
+#include "mifc_column_walk.h"
 #include "mifc_device.h"
 #include "mifc_kernels.h"
 
 namespace mifc {
 
 namespace {
-
-template <int V>
-__device__ __forceinline__ void vi_load(float (&r)[V], const float* p)
-{
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x;
-    r[1] = q.y;
-    r[2] = q.z;
-    r[3] = q.w;
-  } else {
-    r[0] = p[0];
-  }
-}
 
 // the cells of a lane that `m` marks (all of them inside the launch): one 16-byte store where that is all four
 template <int V>
@@ -65,33 +52,6 @@ __device__ __forceinline__ float vi_wave_max(float x)
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
 }
 
-// The body that serves a candidate target runs for a few of the (level, target) pairs only, but everything in it that
-// depends on the level alone (the conversions to double, the defined tests, the logarithms) is loop-invariant to the
-// compiler, which would compute it for EVERY level in front of the candidate loop and keep it in registers (measured:
-// 32 VGPRs per field instead of 12, hundreds of SGPR spills).  Passing a value through this makes it opaque there.
-__device__ __forceinline__ float vi_here(float x)
-{
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ unsigned int vi_here(unsigned int x)
-{
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ int vi_here(int uniform) // the output pointers are fetched from the kernel arguments where they are used
-{
-  asm volatile("" : "+s"(uniform));
-  return uniform;
-}
-
-template <int NF, int V>
-struct Level
-{
-  float c[V];     // field coordinate: as loaded
-  float x[NF][V];
-};
-
 template <bool HYBRID, bool LOG, int NF, int V>
 __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
 {
@@ -107,21 +67,17 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
   const long at = n_mine > 0 ? i0 : 0; // lanes past the end walk column group 0 and neither store nor count
   const float undef = P.undef;
   const int nlev = P.nlev, nt = P.nt;
-  // The per-level scalars are written before the launch and only read here.  Read through the constant address space they
-  // come through the scalar cache; as plain global loads the compiler has to assume that the kernel's own stores may have
-  // changed them and fetches them per lane, in the queue of the field loads.
-  typedef const __attribute__((address_space(4))) float* ConstFloats;
-  typedef const __attribute__((address_space(4))) unsigned int* ConstWords;
+  // the per-level scalars through the scalar cache (mifc_column_walk.h)
   const ConstFloats ab = (ConstFloats)(unsigned long long)P.ab;
   const ConstWords lev_bits = (ConstWords)(unsigned long long)P.lev_bits;
 
-  auto load = [&](Level<NF, V>& L, int k) {
+  auto load = [&](WalkLevel<NF, V>& L, int k) {
     const long off = (long)k * P.in_stride + at;
     if constexpr (!HYBRID)
-      vi_load<V>(L.c, P.coord + off);
+      walk_load<V>(L.c, P.coord + off);
 #pragma unroll
     for (int f = 0; f < NF; ++f)
-      vi_load<V>(L.x[f], P.fields[f] + off);
+      walk_load<V>(L.x[f], P.fields[f] + off);
   };
 
   // An undefined coordinate is carried as NaN: a NaN coordinate never brackets anyway (it fails both comparisons), so
@@ -129,12 +85,12 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
   const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (HYBRID) {
-    vi_load<V>(ps, P.coord + at);
+    walk_load<V>(ps, P.coord + at);
 #pragma unroll
     for (int c = 0; c < V; ++c)
       ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan; // an undefined ps: every level of the cell undefined
   }
-  auto coordinate = [&](const Level<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
+  auto coordinate = [&](const WalkLevel<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
     if constexpr (HYBRID) {
       const float a = ab[k], b = ab[nlev + k];
 #pragma unroll
@@ -152,7 +108,7 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
 
   // level k lives in slot k % 3: at the pair (k, k + 1) the third slot holds level k + 2, already on its way, and the
   // slot of level k is loaded with level k + 3 as soon as the pair is done (two pairs ahead of its first use)
-  Level<NF, V> L[R];
+  WalkLevel<NF, V> L[R];
   load(L[0], 0);
   load(L[1], 1);
   if (2 < nlev)
@@ -174,8 +130,8 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
     for (int d = 0; d < R; ++d) {
       const int k = k0 + d; // the pair (k, k + 1)
       if (k < nlev - 1) {
-        Level<NF, V>& cur = L[d];
-        Level<NF, V>& nx = L[(d + 1) % R];
+        WalkLevel<NF, V>& cur = L[d];
+        WalkLevel<NF, V>& nx = L[(d + 1) % R];
         const unsigned int bits_k1 = lev_bits[k + 1];
         float ck1[V], lo[V], hi[V];
         coordinate(nx, k + 1, bits_k1, ck1);
@@ -212,7 +168,7 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
 #pragma unroll
           for (int c = 0; c < V; ++c) {
             found[c] |= state[c] << t;
-            const float c0 = vi_here(ck[c]), c1 = vi_here(ck1[c]);
+            const float c0 = walk_here(ck[c]), c1 = walk_here(ck1[c]);
             state[c] |= c0 == c1 ? 2u : 0u;
             if constexpr (LOG) {
               state[c] |= !(fminf(c0, c1) > 0.f) ? 4u : 0u;
@@ -221,9 +177,9 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
             } else {
               w[c] = ((double)ct - (double)c0) / ((double)c1 - (double)c0);
             }
-            state[c] = vi_here(state[c]);
+            state[c] = walk_here_v(state[c]);
           }
-          const unsigned int here_k = (unsigned int)vi_here((int)bits_k), here_k1 = (unsigned int)vi_here((int)bits_k1);
+          const unsigned int here_k = (unsigned int)walk_here((int)bits_k), here_k1 = (unsigned int)walk_here((int)bits_k1);
 #pragma unroll
           for (int f = 0; f < NF; ++f) {
             const bool all_k = ((here_k >> f) & 1u) != 0, all_k1 = ((here_k1 >> f) & 1u) != 0;
@@ -232,7 +188,7 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
             unsigned int n = 0;
 #pragma unroll
             for (int c = 0; c < V; ++c) {
-              const float xk = vi_here(cur.x[f][c]), xk1 = vi_here(nx.x[f][c]);
+              const float xk = walk_here(cur.x[f][c]), xk1 = walk_here(nx.x[f][c]);
               const bool ok = (all_k || is_def(xk, undef)) && (all_k1 || is_def(xk1, undef)) && (state[c] & 4u) == 0;
               const double dk = (double)xk;
               const double diff = (double)xk1 - dk;
@@ -242,7 +198,7 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
               hit[c] = (state[c] & 1u) != 0;
               n += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(hit[c] && !ok)); // the whole wave is here
             }
-            vi_store<V>(P.out[vi_here(f)] + (long)(P.t0 + t) * P.out_stride + i0, r, hit);
+            vi_store<V>(P.out[walk_here(f)] + (long)(P.t0 + t) * P.out_stride + i0, r, hit);
             if (n != 0 && (threadIdx.x & 63) == 0)
               atomicAdd(&s_bad[f * VINTERP_PASS + t], n);
           }
@@ -284,7 +240,7 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
     }
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      vi_store<V>(P.out[vi_here(f)] + (long)(P.t0 + t) * P.out_stride + i0, r, miss);
+      vi_store<V>(P.out[walk_here(f)] + (long)(P.t0 + t) * P.out_stride + i0, r, miss);
       if ((threadIdx.x & 63) == 0)
         atomicAdd(&s_bad[f * VINTERP_PASS + t], n);
     }

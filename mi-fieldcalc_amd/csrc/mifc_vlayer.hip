@@ -13,6 +13,7 @@
 // of the walk: per cell and field one double and four floats, per cell the extent, the bounds and a word of bits (bit f:
 // field f has a hole in the layer; CELL_BAD: coordinate or bounds unusable; CELL_ANY: a pair took part).  Undefined
 // cells are counted per wave by ballot into LDS and leave the workgroup as one atomic per field.
+#include "mifc_column_walk.h"
 #include "mifc_device.h"
 #include "mifc_kernels.h"
 
@@ -21,58 +22,6 @@ namespace mifc {
 namespace {
 
 const unsigned int CELL_BAD = 1u << 31, CELL_ANY = 1u << 30;
-
-template <int V>
-__device__ __forceinline__ void vl_load(float (&r)[V], const float* p)
-{
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x;
-    r[1] = q.y;
-    r[2] = q.z;
-    r[3] = q.w;
-  } else {
-    r[0] = p[0];
-  }
-}
-
-// the first n_mine cells of a lane (the ones inside the launch): one 16-byte store where that is all four
-template <int V>
-__device__ __forceinline__ void vl_store(float* p, const float (&r)[V], int n_mine)
-{
-  if constexpr (V == 4) {
-    if (n_mine == 4) {
-      *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < V; ++c)
-    if (c < n_mine)
-      p[c] = r[c];
-}
-
-// makes a value opaque to the compiler where it is used (see vi_here in mifc_vinterp.hip)
-__device__ __forceinline__ float vl_here(float x)
-{
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// the same for a wave-uniform index: the output pointers and product slots are fetched from the kernel arguments where
-// they are used, behind the walk, instead of sitting in SGPRs through it
-__device__ __forceinline__ int vl_here(int uniform)
-{
-  asm volatile("" : "+s"(uniform));
-  return uniform;
-}
-
-template <int NF, int V>
-struct LayerLevel
-{
-  float c[V]; // field coordinate: as loaded
-  float x[NF][V];
-};
 
 // what a cell carries through the walk
 template <int G, int NF, int V>
@@ -100,7 +49,7 @@ __device__ __forceinline__ void vl_candidate(bool part, bool first, float v, flo
 // the levels themselves (a = min, b = max of the two coordinates), so v_a + v_b is x_k + x_k+1 and the candidates are
 // the level values; CLIPPED = true: the general form of rule 5.
 template <bool CLIPPED, int G, int NF, int V>
-__device__ __forceinline__ void vl_pair(LayerState<G, NF, V>& S, const LayerLevel<NF, V>& cur, const LayerLevel<NF, V>& nx, const float (&ck)[V],
+__device__ __forceinline__ void vl_pair(LayerState<G, NF, V>& S, const WalkLevel<NF, V>& cur, const WalkLevel<NF, V>& nx, const float (&ck)[V],
                                         const float (&ck1)[V], const float (&a)[V], const float (&b)[V], const bool (&part)[V], unsigned int all_k,
                                         unsigned int all_k1, float undef)
 {
@@ -134,7 +83,7 @@ __device__ __forceinline__ void vl_pair(LayerState<G, NF, V>& S, const LayerLeve
         const double ia = dk + pa, ib = dk + pb;
         // (compared again for every field: hoisted out of the field loop these five tests per cell are forty SGPRs of
         // lane masks that live through it, more than the wave has to spare)
-        const float ea = vl_here(a[c]), eb = vl_here(b[c]), c0 = vl_here(ck[c]), c1 = vl_here(ck1[c]);
+        const float ea = walk_here(a[c]), eb = walk_here(b[c]), c0 = walk_here(ck[c]), c1 = walk_here(ck1[c]);
         va = ea == c0 ? dk : (ea == c1 ? dk1 : ia);
         vb = eb == c0 ? dk : (eb == c1 ? dk1 : ib);
         const bool rising = c0 <= c1; // a is the end at level k's side
@@ -188,31 +137,29 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
   auto lane_of = [&](const float* uniform_base) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(uniform_base) + lane_bytes); };
   const float undef = P.undef;
   const int nlev = P.nlev, f0 = P.f0;
-  // the per-level scalars through the scalar cache (see mifc_vinterp.hip)
-  typedef const __attribute__((address_space(4))) float* ConstFloats;
-  typedef const __attribute__((address_space(4))) unsigned int* ConstWords;
+  // the per-level scalars through the scalar cache (mifc_column_walk.h)
   const ConstFloats ab = (ConstFloats)(unsigned long long)P.ab;
   const ConstWords lev_bits = (ConstWords)(unsigned long long)P.lev_bits;
 
-  auto load = [&](LayerLevel<NF, V>& L, int k) {
-    const long off = (long)vl_here(k) * P.in_stride + block0; // (k opaque: no induction variable per pointer)
+  auto load = [&](WalkLevel<NF, V>& L, int k) {
+    const long off = (long)walk_here(k) * P.in_stride + block0; // (k opaque: no induction variable per pointer)
     if constexpr (!HYBRID)
-      vl_load<V>(L.c, lane_of(P.coord + off));
+      walk_load<V>(L.c, lane_of(P.coord + off));
 #pragma unroll
     for (int f = 0; f < NF; ++f)
-      vl_load<V>(L.x[f], lane_of(P.fields[f] + off));
+      walk_load<V>(L.x[f], lane_of(P.fields[f] + off));
   };
 
   // an undefined coordinate is carried as NaN: it makes the cell undefined like a NaN that came in as a value (rule 1)
   const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (HYBRID) {
-    vl_load<V>(ps, lane_of(P.coord + block0));
+    walk_load<V>(ps, lane_of(P.coord + block0));
 #pragma unroll
     for (int c = 0; c < V; ++c)
       ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan;
   }
-  auto coordinate = [&](const LayerLevel<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
+  auto coordinate = [&](const WalkLevel<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
     if constexpr (HYBRID) {
       const float a = ab[k], b = ab[nlev + k];
 #pragma unroll
@@ -228,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
     }
   };
 
-  LayerLevel<NF, V> L[R];
+  WalkLevel<NF, V> L[R];
   load(L[0], 0);
   load(L[1], 1);
   if (2 < nlev)
@@ -245,13 +192,13 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
   }
   // rule 2: a bound from a field is tested, the scalars were by the host
   if (P.lo_field != nullptr) {
-    vl_load<V>(lo, lane_of(P.lo_field + block0));
+    walk_load<V>(lo, lane_of(P.lo_field + block0));
 #pragma unroll
     for (int c = 0; c < V; ++c)
       S.bits[c] |= (lo[c] != lo[c] || lo[c] == undef) ? CELL_BAD : 0u;
   }
   if (P.hi_field != nullptr) {
-    vl_load<V>(hi, lane_of(P.hi_field + block0));
+    walk_load<V>(hi, lane_of(P.hi_field + block0));
 #pragma unroll
     for (int c = 0; c < V; ++c)
       S.bits[c] |= (hi[c] != hi[c] || hi[c] == undef) ? CELL_BAD : 0u;
@@ -282,8 +229,8 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
     for (int d = 0; d < R; ++d) {
       const int k = k0 + d; // the pair (k, k + 1)
       if (k < nlev - 1) {
-        LayerLevel<NF, V>& cur = L[d];
-        LayerLevel<NF, V>& nx = L[(d + 1) % R];
+        WalkLevel<NF, V>& cur = L[d];
+        WalkLevel<NF, V>& nx = L[(d + 1) % R];
         const unsigned int bits_k1 = lev_bits[k + 1];
         float ck1[V], a[V], b[V];
         bool part[V];
@@ -335,49 +282,49 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
     }
     if (n != 0 && (threadIdx.x & 63) == 0)
       atomicAdd(&s_bad[f], n);
-    float* const out = P.out[vl_here(f)] + i0;
+    float* const out = P.out[walk_here(f)] + i0;
     const long out_stride = P.out_stride;
     float r[V];
     if constexpr ((G & VLAYER_SUMS) != 0) {
-      if (const int slot = P.slot[vl_here(0)]; slot >= 0) { // MIFC_VLAYER_INTEGRAL
+      if (const int slot = P.slot[walk_here(0)]; slot >= 0) { // MIFC_VLAYER_INTEGRAL
 #pragma unroll
         for (int c = 0; c < V; ++c)
           r[c] = bad[c] ? undef : (float)S.acc[f][c];
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
-      if (const int slot = P.slot[vl_here(1)]; slot >= 0) { // MIFC_VLAYER_MEAN
+      if (const int slot = P.slot[walk_here(1)]; slot >= 0) { // MIFC_VLAYER_MEAN
 #pragma unroll
         for (int c = 0; c < V; ++c) {
           const double mean = S.acc[f][c] / S.ext[c];
           r[c] = bad[c] ? undef : (float)mean;
         }
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
     }
     if constexpr ((G & VLAYER_EXTREMES) != 0) {
-      if (const int slot = P.slot[vl_here(2)]; slot >= 0) { // MIFC_VLAYER_MAX
+      if (const int slot = P.slot[walk_here(2)]; slot >= 0) { // MIFC_VLAYER_MAX
 #pragma unroll
         for (int c = 0; c < V; ++c)
           r[c] = bad[c] ? undef : S.mx[f][c];
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
-      if (const int slot = P.slot[vl_here(3)]; slot >= 0) { // MIFC_VLAYER_MIN
+      if (const int slot = P.slot[walk_here(3)]; slot >= 0) { // MIFC_VLAYER_MIN
 #pragma unroll
         for (int c = 0; c < V; ++c)
           r[c] = bad[c] ? undef : S.mn[f][c];
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
-      if (const int slot = P.slot[vl_here(4)]; slot >= 0) { // MIFC_VLAYER_COORD_OF_MAX
+      if (const int slot = P.slot[walk_here(4)]; slot >= 0) { // MIFC_VLAYER_COORD_OF_MAX
 #pragma unroll
         for (int c = 0; c < V; ++c)
           r[c] = bad[c] ? undef : S.cmx[f][c];
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
-      if (const int slot = P.slot[vl_here(5)]; slot >= 0) { // MIFC_VLAYER_COORD_OF_MIN
+      if (const int slot = P.slot[walk_here(5)]; slot >= 0) { // MIFC_VLAYER_COORD_OF_MIN
 #pragma unroll
         for (int c = 0; c < V; ++c)
           r[c] = bad[c] ? undef : S.cmn[f][c];
-        vl_store<V>(out + (long)slot * out_stride, r, n_mine);
+        walk_store<V>(out + (long)slot * out_stride, r, n_mine);
       }
     }
   }

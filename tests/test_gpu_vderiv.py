@@ -214,6 +214,15 @@ def test_host_call_in_several_bands(gpu_ctx, mifc_env):
     check(gpu_ctx, "field", case[0], case[3], METHODS[1], False, label="bands")
 
 
+def test_host_band_of_one_row_that_exceeds_the_budget(gpu_ctx, mifc_env):
+    mifc_env("MIFC_VDERIV_CHUNK_MIB", 1)
+    # 61 planes of 4300 floats per row are 1049200 bytes, more than the MiB: the band cannot be less than one row, so the three
+    # rows go one at a time, each plane of 4300 floats padded to 4352
+    fields, ps, ab, coord, levs = base(2, 12, 3, 4300, 9)
+    for method in METHODS:
+        check(gpu_ctx, "hybrid", fields, ps, method, False, ab=ab, magnitude="also", label="one-row bands")
+
+
 def test_one_batch_drops_the_leading_axis_and_out_is_honoured(gpu_ctx):
     import torch
 
@@ -241,11 +250,13 @@ def test_refusals_write_nothing(gpu_ctx):
     nf, nlev, ny, nx = 2, 4, 3, 8
     fields_h, ps_h, ab, coord_h, levs = base(nf, nlev, ny, nx, 2)
     x = torch.from_numpy(fields_h).cuda()
-    ps, coord = torch.from_numpy(ps_h).cuda(), torch.from_numpy(coord_h).cuda()
+    batch = nlev * ny * nx
+    room = torch.zeros(batch + ny * nx, dtype=torch.float32, device="cuda")  # a batch of the test's own in front of ps: a magnitude that
+    ps = room[batch:].view(ny, nx).copy_(torch.from_numpy(ps_h))  # ends in ps begins there, whatever else the allocator has put nearby
+    coord = torch.from_numpy(coord_h).cuda()
     sentinel = -4242.5
     outs = torch.full((nf, nlev, ny, nx), sentinel, dtype=torch.float32, device="cuda")
     mags = torch.full((1, nlev, ny, nx), sentinel, dtype=torch.float32, device="cuda")
-    batch = nlev * ny * nx
 
     def call(kind, nx_=nx, ny_=ny, nlev_=nlev, nf_=nf, method=0, fields=None, out_ptrs=None, mag_ptrs=None, coord_ptr=0, a=None, b=None, lv=None,
              fd_out=True, fd_mag=True, sync=True):
@@ -271,53 +282,57 @@ def test_refusals_write_nothing(gpu_ctx):
             torch.cuda.synchronize()
         return rc, gpu_ctx.last_error(), fd, mfd
 
+    # what: (the arguments, the message behind "<entry name>: "; one per kind where the kinds word it differently)
+    null_head = {"hybrid": "a null pointer (fields, ps, alevel or blevel)", "field": "a null pointer (fields or coord)",
+                 "levels": "a null pointer (fields or levels)"}
+    no_level = "level %d: alevel / blevel are no hybrid level (FieldCalculations.cc:298)"
     every = {
-        "nlev < 2": dict(nlev_=1),
-        "nfields 0": dict(nf_=0),
-        "nfields 9": dict(nf_=9),
-        "negative nx": dict(nx_=-1),
-        "negative ny": dict(ny_=-2),
-        "unknown method 2": dict(method=2),
-        "negative method": dict(method=-1),
-        "null fields": dict(fields="null"),
-        "null field": dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)),
-        "null coordinate": dict(coord_ptr=None),
-        "fres and fmag both null": dict(out_ptrs="null", mag_ptrs="null"),
-        "fmag with an odd nfields": dict(nf_=1),
-        "fmag without fdefined_mag": dict(fd_mag=False),
-        "fres without fdefined_out": dict(fd_out=False),
-        "null output": dict(out_ptrs=[outs[0].data_ptr(), None]),
-        "null magnitude": dict(mag_ptrs=[None]),
-        "output is an input": dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]),
-        "output inside an input": dict(out_ptrs=[x[0].data_ptr() + 4 * (batch - 1), outs[1].data_ptr()]),
-        "same output twice": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]),
-        "outputs overlap": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (batch - 1)]),
-        "magnitude overlaps a derivative": dict(mag_ptrs=[outs[1].data_ptr() + 4 * (batch - 1)]),
-        "magnitude is an input": dict(mag_ptrs=[x[0].data_ptr()]),
-        "magnitude only, over an input": dict(out_ptrs="null", mag_ptrs=[x[1].data_ptr() - 4 * (batch - 1)]),
+        "nlev < 2": (dict(nlev_=1), "nlev < 2"),
+        "nfields 0": (dict(nf_=0), "nfields 0 outside 1..8"),
+        "nfields 9": (dict(nf_=9), "nfields 9 outside 1..8"),
+        "negative nx": (dict(nx_=-1), "a negative nx or ny"),
+        "negative ny": (dict(ny_=-2), "a negative nx or ny"),
+        "unknown method 2": (dict(method=2), "unknown method 2"),
+        "negative method": (dict(method=-1), "unknown method -1"),
+        "null fields": (dict(fields="null"), null_head),
+        "null field": (dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)), "a null pointer (fields[1] or fres[1])"),
+        "null coordinate": (dict(coord_ptr=None), null_head),
+        "fres and fmag both null": (dict(out_ptrs="null", mag_ptrs="null"), "fres and fmag are both null: nothing to write"),
+        "fmag with an odd nfields": (dict(nf_=1), "fmag with an odd nfields: a magnitude takes the fields 2j and 2j + 1"),
+        "fmag without fdefined_mag": (dict(fd_mag=False), "fmag without fdefined_mag"),
+        "fres without fdefined_out": (dict(fd_out=False), "fres without fdefined_out"),
+        "null output": (dict(out_ptrs=[outs[0].data_ptr(), None]), "a null pointer (fields[1] or fres[1])"),
+        "null magnitude": (dict(mag_ptrs=[None]), "a null pointer (fmag[0])"),
+        "output is an input": (dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]), "fres[1] overlaps fields[1]"),
+        "output inside an input": (dict(out_ptrs=[x[0].data_ptr() + 4 * (batch - 1), outs[1].data_ptr()]), "fres[0] overlaps fields[0]"),
+        "same output twice": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]), "fres[0] overlaps fres[1]"),
+        "outputs overlap": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (batch - 1)]), "fres[0] overlaps fres[1]"),
+        "magnitude overlaps a derivative": (dict(mag_ptrs=[outs[1].data_ptr() + 4 * (batch - 1)]), "fres[1] overlaps fmag[0]"),
+        "magnitude is an input": (dict(mag_ptrs=[x[0].data_ptr()]), "fmag[0] overlaps fields[0]"),
+        "magnitude only, over an input": (dict(out_ptrs="null", mag_ptrs=[x[1].data_ptr() - 4 * (batch - 1)]), "fmag[0] overlaps fields[0]"),
     }
     only = {
         "hybrid": {
-            "null alevel": dict(a="null"),
-            "null blevel": dict(b="null"),
-            "negative alevel": dict(a=[1.0, -1.0, 2.0, 0.0]),
-            "negative blevel": dict(b=[0.0, 0.1, -0.2, 1.0]),
-            "blevel > 1": dict(b=[0.0, 0.1, 0.2, 1.5]),
-            "alevel = blevel = 0": dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]),
-            "output overlaps ps": dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (ny * nx - 1)]),
-            "magnitude overlaps ps": dict(mag_ptrs=[ps.data_ptr() - 4 * (batch - 1)]),
+            "null alevel": (dict(a="null"), null_head),
+            "null blevel": (dict(b="null"), null_head),
+            "negative alevel": (dict(a=[1.0, -1.0, 2.0, 0.0]), no_level % 1),
+            "negative blevel": (dict(b=[0.0, 0.1, -0.2, 1.0]), no_level % 2),
+            "blevel > 1": (dict(b=[0.0, 0.1, 0.2, 1.5]), no_level % 3),
+            "alevel = blevel = 0": (dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]), no_level % 1),
+            "output overlaps ps": (dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (ny * nx - 1)]), "fres[1] overlaps ps"),
+            "magnitude overlaps ps": (dict(mag_ptrs=[ps.data_ptr() - 4 * (batch - 1)]), "fmag[0] overlaps ps"),
         },
         "field": {
-            "output overlaps coord": dict(out_ptrs=[coord.data_ptr() + 4 * (batch - 1), outs[1].data_ptr()]),
-            "magnitude overlaps coord": dict(mag_ptrs=[coord.data_ptr()]),
+            "output overlaps coord": (dict(out_ptrs=[coord.data_ptr() + 4 * (batch - 1), outs[1].data_ptr()]), "fres[0] overlaps coord"),
+            "magnitude overlaps coord": (dict(mag_ptrs=[coord.data_ptr()]), "fmag[0] overlaps coord"),
         },
-        "levels": {"NaN level": dict(lv=[100, float("nan"), 300, 400])},
+        "levels": {"NaN level": (dict(lv=[100, float("nan"), 300, 400]), "levels[1] is NaN")},
     }
     for kind, name in (("hybrid", "mifc_vderiv_hlevels: "), ("field", "mifc_vderiv_fields: "), ("levels", "mifc_vderiv_levels: ")):
         before = {k: t.clone() for k, t in (("x", x), ("ps", ps), ("coord", coord))}
-        for what, kw in {**every, **only[kind]}.items():
+        for what, (kw, tail) in {**every, **only[kind]}.items():
             rc, err, fd, mfd = call(kind, **kw)
-            assert rc == 0 and err.startswith(name) and len(err) > len(name), (kind, what, err)
+            assert rc == 0 and err == name + (tail[kind] if isinstance(tail, dict) else tail), (kind, what, err)
             assert (outs == sentinel).all().item() and (mags == sentinel).all().item() and (fd == 7).all() and (mfd == 7).all(), (kind, what)
         assert torch.equal(x, before["x"]) and torch.equal(ps, before["ps"]) and torch.equal(coord, before["coord"])
     with pytest.raises(RuntimeError, match="mifc_vderiv_hlevels"):

@@ -173,6 +173,14 @@ def test_host_call_in_several_bands(gpu_ctx, mifc_env):
     check(gpu_ctx, "field", fields, coord, vr.targets_n(33), "linear", False, label="bands, two passes")
 
 
+def test_host_band_without_padding(gpu_ctx, mifc_env):
+    mifc_env("MIFC_VINTERP_CHUNK_MIB", 1)
+    # 2 + 1 + 1 = 4 planes of 32768 floats per row: two rows fill the MiB exactly and their 65536 floats need no padding, so the
+    # planes of the staged band touch; three rows go as a band of two and a band of one
+    fields, ps, ab, coord = base(1, 2, 3, 32768, 9)
+    check(gpu_ctx, "hybrid", fields, ps, [500], "linear", False, ab=ab, label="unpadded band")
+
+
 def test_one_batch_drops_the_leading_axis(gpu_ctx):
     import torch
 
@@ -219,46 +227,49 @@ def test_refusals_write_nothing(gpu_ctx):
         return rc, gpu_ctx.last_error(), fd
 
     nan = float("nan")
+    # what: (the arguments, the message behind "<entry name>: "; a pair where the two entries word it differently)
+    null_head = ("a null pointer (fields, ps, alevel, blevel, targets, fres or fdefined_out)", "a null pointer (fields, coord, targets, fres or fdefined_out)")
+    no_level = "level %d: alevel / blevel are no hybrid level (FieldCalculations.cc:298)"
     both = {
-        "nlev < 2": dict(nlev_=1),
-        "nfields 0": dict(nf_=0),
-        "nfields 9": dict(nf_=9),
-        "ntargets 0": dict(nt_=0),
-        "ntargets 65": dict(nt_=65),
-        "negative nx": dict(nx_=-1),
-        "negative ny": dict(ny_=-2),
-        "null fields": dict(fields="null"),
-        "null field": dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)),
-        "null coordinate": dict(coord_ptr=None),
-        "null targets": dict(tg=False),
-        "null fres": dict(out_ptrs="null"),
-        "null output": dict(out_ptrs=[outs[0].data_ptr(), None]),
-        "null flags out": dict(fd_out=False),
-        "unknown method": dict(method=2),
-        "negative method": dict(method=-1),
-        "NaN target": dict(targets=(850.0, nan, 300.0)),
-        "LOG with a zero target": dict(method=1, targets=(850.0, 0.0, 300.0)),
-        "LOG with a negative target": dict(method=1, targets=(-850.0, 500.0, 300.0)),
-        "output is an input": dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]),
-        "output inside an input": dict(out_ptrs=[x[0].data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]),
-        "same output twice": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]),
-        "outputs overlap": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (nt * cells - 1)]),
+        "nlev < 2": (dict(nlev_=1), "nlev < 2"),
+        "nfields 0": (dict(nf_=0), "nfields 0 outside 1..8"),
+        "nfields 9": (dict(nf_=9), "nfields 9 outside 1..8"),
+        "ntargets 0": (dict(nt_=0), "ntargets 0 outside 1..64"),
+        "ntargets 65": (dict(nt_=65), "ntargets 65 outside 1..64"),
+        "negative nx": (dict(nx_=-1), "a negative nx or ny"),
+        "negative ny": (dict(ny_=-2), "a negative nx or ny"),
+        "null fields": (dict(fields="null"), null_head),
+        "null field": (dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)), "a null pointer (fields[1] or fres[1])"),
+        "null coordinate": (dict(coord_ptr=None), null_head),
+        "null targets": (dict(tg=False), null_head),
+        "null fres": (dict(out_ptrs="null"), null_head),
+        "null output": (dict(out_ptrs=[outs[0].data_ptr(), None]), "a null pointer (fields[1] or fres[1])"),
+        "null flags out": (dict(fd_out=False), null_head),
+        "unknown method": (dict(method=2), "unknown method 2 (MIFC_VINTERP_LINEAR or MIFC_VINTERP_LOG)"),
+        "negative method": (dict(method=-1), "unknown method -1 (MIFC_VINTERP_LINEAR or MIFC_VINTERP_LOG)"),
+        "NaN target": (dict(targets=(850.0, nan, 300.0)), "targets[1] is NaN"),
+        "LOG with a zero target": (dict(method=1, targets=(850.0, 0.0, 300.0)), "MIFC_VINTERP_LOG with targets[1] <= 0"),
+        "LOG with a negative target": (dict(method=1, targets=(-850.0, 500.0, 300.0)), "MIFC_VINTERP_LOG with targets[0] <= 0"),
+        "output is an input": (dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]), "fres[1] overlaps fields[1]"),
+        "output inside an input": (dict(out_ptrs=[x[0].data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]), "fres[0] overlaps fields[0]"),
+        "same output twice": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]), "fres[0] overlaps fres[1]"),
+        "outputs overlap": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (nt * cells - 1)]), "fres[0] overlaps fres[1]"),
     }
     hybrid_only = {
-        "null alevel": dict(a="null"),
-        "null blevel": dict(b="null"),
-        "negative alevel": dict(a=[1.0, -1.0, 2.0, 0.0]),
-        "negative blevel": dict(b=[0.0, 0.1, -0.2, 1.0]),
-        "blevel > 1": dict(b=[0.0, 0.1, 0.2, 1.5]),
-        "alevel = blevel = 0": dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]),
-        "output overlaps ps": dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (cells - 1)]),
+        "null alevel": (dict(a="null"), null_head),
+        "null blevel": (dict(b="null"), null_head),
+        "negative alevel": (dict(a=[1.0, -1.0, 2.0, 0.0]), no_level % 1),
+        "negative blevel": (dict(b=[0.0, 0.1, -0.2, 1.0]), no_level % 2),
+        "blevel > 1": (dict(b=[0.0, 0.1, 0.2, 1.5]), no_level % 3),
+        "alevel = blevel = 0": (dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]), no_level % 1),
+        "output overlaps ps": (dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (cells - 1)]), "fres[1] overlaps ps"),
     }
-    field_only = {"output overlaps coord": dict(out_ptrs=[coord.data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()])}
+    field_only = {"output overlaps coord": (dict(out_ptrs=[coord.data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]), "fres[0] overlaps coord")}
     for hybrid, name, cases in ((True, "mifc_vinterp_hlevels: ", {**both, **hybrid_only}), (False, "mifc_vinterp_fields: ", {**both, **field_only})):
         before = {k: t.clone() for k, t in (("x", x), ("ps", ps), ("coord", coord))}
-        for what, kw in cases.items():
+        for what, (kw, tail) in cases.items():
             rc, err, fd = call(hybrid, **kw)
-            assert rc == 0 and err.startswith(name) and len(err) > len(name), (what, err)
+            assert rc == 0 and err == name + (tail if isinstance(tail, str) else tail[0 if hybrid else 1]), (what, err)
             assert (outs == sentinel).all().item() and (fd == 7).all(), what
         assert torch.equal(x, before["x"]) and torch.equal(ps, before["ps"]) and torch.equal(coord, before["coord"])
     with pytest.raises(RuntimeError, match="mifc_vinterp_hlevels"):

@@ -235,53 +235,58 @@ def test_refusals_write_nothing(gpu_ctx):
         return rc, gpu_ctx.last_error(), fd
 
     nan = float("nan")
+    # what: (the arguments, the message behind "<entry name>: "; a pair where the two entries word it differently)
+    null_head = ("a null pointer (fields, ps, alevel, blevel, products, fres or fdefined_out)", "a null pointer (fields, coord, products, fres or fdefined_out)")
+    no_level = "level %d: alevel / blevel are no hybrid level (FieldCalculations.cc:298)"
+    no_product = "products[%d] = %d is no MIFC_VLAYER_* product"
+    empty = "the layer is empty: not lo < hi"
     both = {
-        "nlev < 2": dict(nlev_=1),
-        "nfields 0": dict(nf_=0),
-        "nfields 9": dict(nf_=9),
-        "nproducts 0": dict(np_=0),
-        "nproducts 7": dict(np_=7),
-        "unknown product 0": dict(products=(1, 0, 5)),
-        "unknown product 7": dict(products=(7, 3, 5)),
-        "negative product": dict(products=(1, 3, -2)),
-        "repeated product": dict(products=(1, 3, 1)),
-        "negative nx": dict(nx_=-1),
-        "negative ny": dict(ny_=-2),
-        "null fields": dict(fields="null"),
-        "null field": dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)),
-        "null coordinate": dict(coord_ptr=None),
-        "null products": dict(pr=False),
-        "null fres": dict(out_ptrs="null"),
-        "null output": dict(out_ptrs=[outs[0].data_ptr(), None]),
-        "null flags out": dict(fd_out=False),
-        "lo == hi": dict(lo=500.0, hi=500.0),
-        "lo > hi": dict(lo=850.0, hi=300.0),
-        "NaN lo": dict(lo=nan),
-        "NaN hi": dict(hi=nan),
-        "NaN scalar lo beside a hi field": dict(lo=nan, hi_ptr=hif.data_ptr()),
-        "NaN scalar hi beside a lo field": dict(hi=nan, lo_ptr=lof.data_ptr()),
-        "output is an input": dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]),
-        "output inside an input": dict(out_ptrs=[x[0].data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]),
-        "same output twice": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]),
-        "outputs overlap": dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (npr * cells - 1)]),
-        "output overlaps lo_field": dict(lo_ptr=outs[1].data_ptr() + 4 * (npr * cells - 1)),
-        "output overlaps hi_field": dict(hi_ptr=outs[0].data_ptr()),
+        "nlev < 2": (dict(nlev_=1), "nlev < 2"),
+        "nfields 0": (dict(nf_=0), "nfields 0 outside 1..8"),
+        "nfields 9": (dict(nf_=9), "nfields 9 outside 1..8"),
+        "nproducts 0": (dict(np_=0), "nproducts 0 outside 1..6"),
+        "nproducts 7": (dict(np_=7), "nproducts 7 outside 1..6"),
+        "unknown product 0": (dict(products=(1, 0, 5)), no_product % (1, 0)),
+        "unknown product 7": (dict(products=(7, 3, 5)), no_product % (0, 7)),
+        "negative product": (dict(products=(1, 3, -2)), no_product % (2, -2)),
+        "repeated product": (dict(products=(1, 3, 1)), "product 1 asked for twice"),
+        "negative nx": (dict(nx_=-1), "a negative nx or ny"),
+        "negative ny": (dict(ny_=-2), "a negative nx or ny"),
+        "null fields": (dict(fields="null"), null_head),
+        "null field": (dict(fields=(ctypes.c_void_p * nf)(x[0].data_ptr(), None)), "a null pointer (fields[1] or fres[1])"),
+        "null coordinate": (dict(coord_ptr=None), null_head),
+        "null products": (dict(pr=False), null_head),
+        "null fres": (dict(out_ptrs="null"), null_head),
+        "null output": (dict(out_ptrs=[outs[0].data_ptr(), None]), "a null pointer (fields[1] or fres[1])"),
+        "null flags out": (dict(fd_out=False), null_head),
+        "lo == hi": (dict(lo=500.0, hi=500.0), empty),
+        "lo > hi": (dict(lo=850.0, hi=300.0), empty),
+        "NaN lo": (dict(lo=nan), empty),  # (not NaN < hi: the two scalars are tested against each other first)
+        "NaN hi": (dict(hi=nan), empty),
+        "NaN scalar lo beside a hi field": (dict(lo=nan, hi_ptr=hif.data_ptr()), "a NaN bound"),
+        "NaN scalar hi beside a lo field": (dict(hi=nan, lo_ptr=lof.data_ptr()), "a NaN bound"),
+        "output is an input": (dict(out_ptrs=[outs[0].data_ptr(), x[1].data_ptr()]), "fres[1] overlaps fields[1]"),
+        "output inside an input": (dict(out_ptrs=[x[0].data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]), "fres[0] overlaps fields[0]"),
+        "same output twice": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr()]), "fres[0] overlaps fres[1]"),
+        "outputs overlap": (dict(out_ptrs=[outs[0].data_ptr(), outs[0].data_ptr() + 4 * (npr * cells - 1)]), "fres[0] overlaps fres[1]"),
+        "output overlaps lo_field": (dict(lo_ptr=outs[1].data_ptr() + 4 * (npr * cells - 1)), "fres[1] overlaps lo_field"),
+        "output overlaps hi_field": (dict(hi_ptr=outs[0].data_ptr()), "fres[0] overlaps hi_field"),
     }
     hybrid_only = {
-        "null alevel": dict(a="null"),
-        "null blevel": dict(b="null"),
-        "negative alevel": dict(a=[1.0, -1.0, 2.0, 0.0]),
-        "negative blevel": dict(b=[0.0, 0.1, -0.2, 1.0]),
-        "blevel > 1": dict(b=[0.0, 0.1, 0.2, 1.5]),
-        "alevel = blevel = 0": dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]),
-        "output overlaps ps": dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (cells - 1)]),
+        "null alevel": (dict(a="null"), null_head),
+        "null blevel": (dict(b="null"), null_head),
+        "negative alevel": (dict(a=[1.0, -1.0, 2.0, 0.0]), no_level % 1),
+        "negative blevel": (dict(b=[0.0, 0.1, -0.2, 1.0]), no_level % 2),
+        "blevel > 1": (dict(b=[0.0, 0.1, 0.2, 1.5]), no_level % 3),
+        "alevel = blevel = 0": (dict(a=[1.0, 0.0, 2.0, 0.0], b=[0.0, 0.0, 0.5, 1.0]), no_level % 1),
+        "output overlaps ps": (dict(out_ptrs=[outs[0].data_ptr(), ps.data_ptr() + 4 * (cells - 1)]), "fres[1] overlaps ps"),
     }
-    field_only = {"output overlaps coord": dict(out_ptrs=[coord.data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()])}
+    field_only = {"output overlaps coord": (dict(out_ptrs=[coord.data_ptr() + 4 * (nlev * cells - 1), outs[1].data_ptr()]), "fres[0] overlaps coord")}
     for hybrid, name, cases in ((True, "mifc_vlayer_hlevels: ", {**both, **hybrid_only}), (False, "mifc_vlayer_fields: ", {**both, **field_only})):
         before = {k: t.clone() for k, t in (("x", x), ("ps", ps), ("coord", coord), ("lo", lof), ("hi", hif))}
-        for what, kw in cases.items():
+        for what, (kw, tail) in cases.items():
             rc, err, fd = call(hybrid, **kw)
-            assert rc == 0 and err.startswith(name) and len(err) > len(name), (what, err)
+            assert rc == 0 and err == name + (tail if isinstance(tail, str) else tail[0 if hybrid else 1]), (what, err)
             assert (outs == sentinel).all().item() and (fd == 7).all(), what
         assert torch.equal(x, before["x"]) and torch.equal(ps, before["ps"]) and torch.equal(coord, before["coord"])
         assert torch.equal(lof, before["lo"]) and torch.equal(hif, before["hi"])
