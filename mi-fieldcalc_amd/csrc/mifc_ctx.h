@@ -1,7 +1,8 @@
 // mifc_ctx.h -- internals shared by the host-side translation units of the C
-// ABI (mifc_capi*.hip, mifc_slab.hip, mifc_graph.hip, ...): the context, the
-// per-call staging of host fields and the small helpers every entry point
-// uses.  Implemented in mifc_ctx.hip.  Not installed.
+// ABI (mifc_capi.hip and one mifc_capi_<family>.hip per operator family,
+// mifc_slab.hip, mifc_graph.hip, ...): the context, the per-call staging of
+// host fields and the small helpers every entry point uses, the reference's
+// unit / compute remaps among them.  Implemented in mifc_ctx.hip.  Not installed.
 #ifndef MIFC_CTX_H
 #define MIFC_CTX_H
 
@@ -11,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -215,6 +217,68 @@ const float K_KAPPA = 287.f / 1004.f;
 inline bool bad_hlevel(float a, float b) // FieldCalculations.cc:298-301
 {
   return (a < 0.0) || (b < 0.0) || (a == 0.0 && b == 0.0) || (b > 1.0);
+}
+
+inline bool unit_is(const char* unit, const char* what)
+{
+  return unit && std::strcmp(unit, what) == 0;
+}
+
+// *leveltemp (:340-345, :1060-1065): below compute 3 the unit decides between Celsius and Kelvin
+inline int remap_temp_compute(const char* unit, int compute)
+{
+  if (compute < 3) {
+    if (unit_is(unit, "celsius"))
+      return 1;
+    if (unit_is(unit, "kelvin"))
+      return 2;
+  }
+  return compute;
+}
+
+// *levelhum (:422-425, :1174-1177, :1417-1420): the dew-point variants come in a Celsius and a Kelvin numbering
+inline int remap_hum_compute(const char* unit, int compute)
+{
+  if (compute > 8 && unit_is(unit, "celsius"))
+    return compute - 4;
+  if (compute > 4 && compute <= 8 && unit_is(unit, "kelvin"))
+    return compute + 4;
+  return compute;
+}
+
+inline float hum_tdconv(int compute) // :437, :1181, :1423, after the remap
+{
+  return (compute >= 9) ? K_T0 : 0;
+}
+
+inline int hum_kind_ah(int compute) // numbering of alevelhum / hlevelhum (:1157-1164), after the remap
+{
+  if (compute <= 2)
+    return mifc::HUM_Q_RH;
+  if (compute <= 4)
+    return mifc::HUM_RH_Q;
+  if (compute == 5 || compute == 6 || compute == 9 || compute == 10)
+    return mifc::HUM_Q_TD;
+  return mifc::HUM_RH_TD;
+}
+
+inline bool host_pipeline_enabled()
+{
+  return mifc::env().host_pipeline; // MIFC_HOST_PIPELINE=0: stage whole batches (for A/B measurements)
+}
+
+// what every single-field elementwise call starts from
+inline mifc::EwiseParams ewise_base(int op, int nx, int ny, const int* fdefined, float undef)
+{
+  mifc::EwiseParams P;
+  std::memset(&P, 0, sizeof P);
+  P.op = op;
+  P.n = nx * ny;
+  P.all_defined = (*fdefined == MIFC_ALL_DEFINED);
+  P.count = 1;
+  P.undef = undef;
+  P.unit_scale = 100.f;
+  return P;
 }
 
 } // namespace mifc_host

@@ -19,8 +19,8 @@
 // an RCCL group on the host: a 500 x 4000 slab is 13 us of kernel time); MIFC_SLAB_GRAPH=0, or a capture the runtime
 // refuses, falls back to enqueuing the sequence directly.  A slab is a level BATCH ([nlev][ny_local + 2][nx]): one exchange
 // of nlev rows per neighbour and field amortises the step over the levels.
-#include "mifc_ctx.h"
 #include "mifc_rccl.h"
+#include "mifc_stencil_host.h"
 
 #include <cstring>
 #include <new>
@@ -64,39 +64,22 @@ bool rccl_ok(mifc_ctx* c, const mifc::RcclApi* api, ncclResult_t r, const char* 
 int launch_rows(mifc_slab_plan* p, int row_begin, int row_end)
 {
   mifc_ctx* c = p->c;
-  mifc::StencilParams P;
-  std::memset(&P, 0, sizeof P);
-  P.op = mifc::ST_VORTDIV;
-  P.out0 = p->rv;
-  P.out1 = p->dv;
-  if (!p->rv) {
-    P.op = mifc::ST_DIVERGENCE;
-    P.out0 = p->dv;
-    P.out1 = nullptr;
-  } else if (!p->dv) {
-    P.op = mifc::ST_RELVORT;
+  // owned row 0 of level 0; the halo rows sit directly before and after the owned rows of a level
+  StencilCall sc = {mifc::ST_VORTDIV, p->nx, p->nyg, p->nlev, p->u + p->nx, p->v + p->nx, p->xm, p->ym, nullptr, p->rv, p->dv};
+  sc.j0 = p->j0;
+  sc.ny_local = p->nyl;
+  sc.in_level_stride = (long)(p->nyl + 2) * p->nx;
+  sc.out_level_stride = (long)p->nyl * p->nx;
+  if (row_begin != 0 || row_end != p->nyl) {
+    sc.row_begin = row_begin;
+    sc.row_end = row_end;
   }
-  P.nx = p->nx;
-  P.ny_global = p->nyg;
-  P.j0 = p->j0;
-  P.ny_local = p->nyl;
-  P.nlev = p->nlev;
-  P.f0 = p->u + p->nx; // owned row 0 of level 0; the halo rows sit directly before and after the owned rows of a level
-  P.f1 = p->v + p->nx;
-  P.xmapr = p->xm;
-  P.ymapr = p->ym;
-  P.in_level_stride = (long)(p->nyl + 2) * p->nx;
-  P.out_level_stride = (long)p->nyl * p->nx;
-  P.undef = p->undef;
+  mifc::StencilParams P = stencil_params(sc, p->undef);
   P.every_level_all_defined = (p->fdef == MIFC_ALL_DEFINED) ? 1 : 0;
   P.all_defined = nullptr;
   P.n_undefined = p->counts;
   P.partials = p->d_partials; // the launches of a step follow each other on one stream
   P.partials_cap = p->partials_cap;
-  if (row_begin != 0 || row_end != p->nyl) {
-    P.row_begin = row_begin;
-    P.row_end = row_end;
-  }
   MIFC_LAUNCH(c, mifc::launch_stencil(P, c->stream));
   return 1;
 }

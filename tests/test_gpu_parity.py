@@ -971,6 +971,188 @@ def test_stencil_levels_enqueue_equals_the_synchronous_call(gpu_ctx, oracle):
         gpu_ctx.stencil_levels_enqueue("divergence", du, dv, dxm, dym, None, o0, fdefined=flags, n_undefined=None)
 
 
+def test_level_batch_deeper_than_the_one_kernel_preparation(gpu_ctx, oracle):
+    """2049 levels of 8 x 5: one more than the flags-and-counters kernel in front of a stencil launch takes, so the flags go up
+    by a copy and the counters are zeroed by fills.  The synchronous call, the enqueue call and the three-output call give
+    the per-level reference fields bit for bit; flags from classify(count, domain), counters prefilled with 99.  Then one call
+    of each with every level ALL_DEFINED and no counter array."""
+    import torch
+
+    import mi_fieldcalc_amd as fc
+
+    nx, ny, nlev = 8, 5, 2049
+    u, v, xm, ym, _ = _levels_inputs(nx, ny, nlev, 2049, mixed=False)
+    flags = np.where(np.arange(nlev) % 6 == 0, ALL, SOME).astype(np.int32)
+    for l, (j, i) in ((1, (2, 3)), (1027, (1, 6)), (2048, (3, 1))):  # tested levels, interior cells
+        u[l, j, i] = cases.UNDEF
+    v[2048, 0, 0] = cases.UNDEF  # row 0: counts for ff only
+    u[6, 2, 2] = cases.UNDEF  # an ALL_DEFINED level: not tested, computed like a number (a flag that went up wrong would show)
+    rv_e, dv_e, fo_e = _expect_levels(oracle, u, v, xm, ym, flags)
+    ff_e, fof_e = np.empty_like(u), np.empty(nlev, np.int32)
+    for l in range(nlev):
+        ok, ff_e[l], fof_e[l] = oracle.call("vectorabs", nx, ny, u[l], v[l], fdefined=int(flags[l]))
+        assert ok
+    du, dvv, dxm, dym = (torch.from_numpy(a).cuda() for a in (u, v, xm, ym))
+    dom = nx * ny - 2 * nx
+
+    def flags_of(counts, domain):
+        return np.array([ALL if flags[l] == ALL else fc.classify(int(c), domain) for l, c in enumerate(counts.cpu().numpy())])
+
+    def same(t, e):
+        return cases.same_bits(t.cpu().numpy(), e, nan_payload=False)
+
+    (rv, dg), fo = gpu_ctx.stencil_levels("vortdiv", du, dvv, dxm, dym, fdefined=flags)
+    assert same(rv, rv_e) and same(dg, dv_e) and np.array_equal(fo, fo_e)
+    rv, dg, ff = torch.empty_like(du), torch.empty_like(du), torch.empty_like(du)
+    cnt = torch.full((nlev,), 99, dtype=torch.int64, device="cuda")
+    assert gpu_ctx.stencil_levels_enqueue("vortdiv", du, dvv, dxm, dym, None, rv, dg, fdefined=flags, n_undefined=cnt)
+    torch.cuda.synchronize()
+    assert same(rv, rv_e) and same(dg, dv_e) and np.array_equal(flags_of(cnt, dom), fo_e)
+    rv, dg = torch.empty_like(du), torch.empty_like(du)
+    cnt.fill_(99)
+    cnt_ff = torch.full((nlev,), 99, dtype=torch.int64, device="cuda")
+    assert gpu_ctx.vortdiv_ff_levels_enqueue(du, dvv, dxm, dym, rv, dg, ff, fdefined=flags, n_undefined=cnt, n_undefined_ff=cnt_ff)
+    torch.cuda.synchronize()
+    assert same(rv, rv_e) and same(dg, dv_e) and same(ff, ff_e)
+    assert np.array_equal(flags_of(cnt, dom), fo_e) and np.array_equal(flags_of(cnt_ff, nx * ny), fof_e)
+    # every level ALL_DEFINED: nothing is tested, no counters
+    flags[:] = ALL
+    rv_e, dv_e, fo_e = _expect_levels(oracle, u, v, xm, ym, flags)
+    for l in (1, 1027, 2048):  # (level 6 was ALL_DEFINED before)
+        ok, ff_e[l], _ = oracle.call("vectorabs", nx, ny, u[l], v[l], fdefined=ALL)
+    (rv, dg), fo = gpu_ctx.stencil_levels("vortdiv", du, dvv, dxm, dym, fdefined=flags)
+    assert same(rv, rv_e) and same(dg, dv_e) and np.array_equal(fo, fo_e)
+    rv, dg = torch.empty_like(du), torch.empty_like(du)
+    assert gpu_ctx.stencil_levels_enqueue("vortdiv", du, dvv, dxm, dym, None, rv, dg, fdefined=flags, n_undefined=None)
+    torch.cuda.synchronize()
+    assert same(rv, rv_e) and same(dg, dv_e)
+    rv, dg, ff = torch.empty_like(du), torch.empty_like(du), torch.empty_like(du)
+    assert gpu_ctx.vortdiv_ff_levels_enqueue(du, dvv, dxm, dym, rv, dg, ff, fdefined=flags, n_undefined=None, n_undefined_ff=None)
+    torch.cuda.synchronize()
+    assert same(rv, rv_e) and same(dg, dv_e) and same(ff, ff_e)
+
+
+def test_enqueue_counters_under_counts_accumulate(gpu_ctx):
+    """mifc_counts_accumulate: mifc_stencil_levels_enqueue adds to the caller's counters instead of zeroing them.
+    mifc_vortdiv_ff_levels_enqueue is the documented exception: it zeroes both of its counter arrays whatever the mode."""
+    import torch
+
+    nx, ny, nlev = 8, 5, 3
+    u, v, xm, ym, _ = _levels_inputs(nx, ny, nlev, 77, mixed=False)
+    u[0, 2, 3] = cases.UNDEF
+    u[1, 1, 1] = u[1, 3, 6] = cases.UNDEF
+    v[2, 0, 2] = cases.UNDEF
+    flags = np.full(nlev, SOME, np.int32)
+    du, dvv, dxm, dym = (torch.from_numpy(a).cuda() for a in (u, v, xm, ym))
+    rv, dg, ff = torch.empty_like(du), torch.empty_like(du), torch.empty_like(du)
+
+    def counters(fill):
+        return torch.full((nlev,), fill, dtype=torch.int64, device="cuda")
+
+    fresh, fresh2, fresh_ff = counters(99), counters(99), counters(99)
+    assert gpu_ctx.stencil_levels_enqueue("vortdiv", du, dvv, dxm, dym, None, rv, dg, fdefined=flags, n_undefined=fresh)
+    assert gpu_ctx.vortdiv_ff_levels_enqueue(du, dvv, dxm, dym, rv, dg, ff, fdefined=flags, n_undefined=fresh2, n_undefined_ff=fresh_ff)
+    torch.cuda.synchronize()
+    assert torch.equal(fresh, fresh2) and int(fresh[:2].min()) > 0 and fresh_ff.tolist() == [1, 2, 1]
+    cnt, cnt2, cnt_ff = counters(7), counters(7), counters(7)
+    gpu_ctx.counts_accumulate(True)
+    try:
+        assert gpu_ctx.stencil_levels_enqueue("vortdiv", du, dvv, dxm, dym, None, rv, dg, fdefined=flags, n_undefined=cnt)
+        assert gpu_ctx.vortdiv_ff_levels_enqueue(du, dvv, dxm, dym, rv, dg, ff, fdefined=flags, n_undefined=cnt2, n_undefined_ff=cnt_ff)
+        torch.cuda.synchronize()
+    finally:
+        gpu_ctx.counts_accumulate(False)
+    assert torch.equal(cnt, fresh + 7)
+    assert torch.equal(cnt2, fresh) and torch.equal(cnt_ff, fresh_ff)
+
+
+def test_level_batch_entries_refuse_like_before(gpu_ctx):
+    """What the level-batch entries refuse, and in which words: an argument refusal returns false with an empty
+    mifc_last_error(), the others name the entry (the strided entry's missing-counters text names mifc_vortdiv_levels_enqueue,
+    the synchronous mifc_hlevel_derived_levels the batch entry).  No refused call writes an output field."""
+    import torch
+
+    import mi_fieldcalc_amd as fc
+    import mi_fieldcalc_amd.synth as synth
+
+    nx, ny, nlev = 8, 5, 3
+    xm, ym, fcor = synth.grid_maps(nx, ny)
+    u, v = synth.wind(nx, ny, 5, nlev=nlev)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    du, dv, dxm, dym, dfc = (dev(a) for a in (u, v, xm, ym, fcor))
+    o0, o1, o2 = (torch.full_like(du, 777.0) for _ in range(3))
+    cnt, cnt_ff = torch.zeros(nlev, dtype=torch.int64, device="cuda"), torch.zeros(nlev, dtype=torch.int64, device="cuda")
+    some, all_ = np.full(nlev, SOME, np.int32), np.full(nlev, ALL, np.int32)
+
+    def refused(text, fn, *args, **kw):
+        if text:
+            with pytest.raises(RuntimeError) as ei:
+                fn(*args, **kw)
+            assert str(ei.value).split(": ", 1)[1] == text
+        else:
+            assert not fn(*args, **kw)
+        assert gpu_ctx.last_error() == text
+
+    ctx = gpu_ctx
+    # nx = 2
+    n2 = [torch.zeros((nlev, ny, 2), device="cuda") for _ in range(2)] + [torch.zeros((ny, 2), device="cuda") for _ in range(2)]
+    p0, p1, p2 = (torch.full((nlev, ny, 2), 777.0, device="cuda") for _ in range(3))
+    refused("", ctx.stencil_levels, "vortdiv", *n2, fdefined=some, out0=p0, out1=p1)
+    refused("", ctx.stencil_levels_enqueue, "vortdiv", *n2, None, p0, p1, fdefined=some, n_undefined=cnt)
+    refused("", ctx.vortdiv_levels_enqueue, *n2, p0, p1, fdefined=some, n_undefined=cnt)
+    refused("", ctx.vortdiv_ff_levels_enqueue, *n2, p0, p1, p2, fdefined=some, n_undefined=cnt, n_undefined_ff=cnt_ff)
+    assert all(bool((p == 777.0).all()) for p in (p0, p1, p2))
+    # nlev = 0 (the wrappers would pass null pointers for empty tensors: the C entries directly, on real fields)
+    ctx.use_torch_stream()
+    ptr = [t.data_ptr() for t in (du, dv, dxm, dym)]
+    outs = [t.data_ptr() for t in (o0, o1, o2)]
+    n = nx * ny
+    refused("", ctx._call, "mifc_stencil_levels", [3, nx, ny, 0] + ptr + [None] + outs[:2] + [some.copy(), float(fc.UNDEF), fc.MEM_DEVICE])
+    refused("", ctx._call, "mifc_stencil_levels_enqueue", [3, nx, ny, 0] + ptr + [None] + outs[:2] + [some, float(fc.UNDEF), cnt.data_ptr()])
+    refused("", ctx._call, "mifc_vortdiv_levels_strided_enqueue", [nx, ny, 0] + ptr + outs[:2] + [n, n, some, float(fc.UNDEF), cnt.data_ptr()])
+    refused("", ctx._call, "mifc_vortdiv_ff_levels_enqueue", [nx, ny, 0] + ptr + outs + [some, float(fc.UNDEF), cnt.data_ptr(), cnt_ff.data_ptr()])
+    # operator classes: a missing second input, Coriolis field, second output, any output
+    refused("", ctx.stencil_levels, "jacobian", du, None, dxm, dym, fdefined=some, out0=o0)
+    refused("", ctx.stencil_levels_enqueue, "absvort", du, dv, dxm, dym, None, o0, fdefined=some, n_undefined=cnt)
+    refused("", ctx.stencil_levels_enqueue, "ilevelgwind", du, None, dxm, dym, dfc, o0, None, fdefined=some, n_undefined=cnt)
+    refused("", ctx.stencil_levels_enqueue, "vortdiv", du, dv, dxm, dym, None, None, None, fdefined=some, n_undefined=cnt)
+    # counters
+    refused("mifc_stencil_levels_enqueue: n_undefined_dev is required unless every level is ALL_DEFINED",
+            ctx.stencil_levels_enqueue, "vortdiv", du, dv, dxm, dym, None, o0, o1, fdefined=some, n_undefined=None)
+    refused("mifc_vortdiv_levels_strided_enqueue: a level stride is smaller than one field",
+            ctx._call, "mifc_vortdiv_levels_strided_enqueue", [nx, ny, nlev] + ptr + outs[:2] + [n - 1, n, some, float(fc.UNDEF), None])
+    refused("mifc_vortdiv_levels_strided_enqueue: a level stride is smaller than one field",
+            ctx._call, "mifc_vortdiv_levels_strided_enqueue", [nx, ny, nlev] + ptr + outs[:2] + [n, n - 1, some, float(fc.UNDEF), cnt.data_ptr()])
+    refused("mifc_vortdiv_levels_enqueue: n_undefined_dev is required unless every level is ALL_DEFINED",
+            ctx.vortdiv_levels_enqueue, du, dv, dxm, dym, o0, o1, fdefined=some, n_undefined=None)
+    for a, b in ((cnt, None), (None, cnt_ff)):
+        refused("mifc_vortdiv_ff_levels_enqueue: both counter arrays are required unless every level is ALL_DEFINED",
+                ctx.vortdiv_ff_levels_enqueue, du, dv, dxm, dym, o0, o1, o2, fdefined=some, n_undefined=a, n_undefined_ff=b)
+    # the f1 operators
+    qv = dict(f1=dv, xmapr=dxm, ymapr=dym, fcoriolis=dfc, fdefined=all_, out0=o0)
+    refused("", ctx.stencil_levels_ex, "plevelqvector", du, level_scalars=[850.0, 0.0, 500.0], compute=1, **qv)
+    refused("", ctx.stencil_levels_ex, "plevelqvector", du, level_scalars=[850.0, 700.0, 500.0], compute=5, **qv)
+    refused("", ctx.stencil_levels_ex, "advection", du, f1=du, f2=None, xmapr=dxm, ymapr=dym, scalar=3.0, fdefined=some, out0=o0)
+    assert all(bool((o == 777.0).all()) for o in (o0, o1, o2))
+    # the derived batch: a cell count that is no multiple of 4, in each entry's words; a temperature variant it does not offer
+    al, bl = synth.hybrid_levels(nlev)
+    t7, ps7 = torch.full((nlev, 5, 7), 280.0, device="cuda"), torch.full((5, 7), 1000.0, device="cuda")
+    q7 = torch.full((nlev, 5, 7), 777.0, device="cuda")
+    cnt5 = torch.zeros(5 * nlev, dtype=torch.int64, device="cuda")
+    batch = "mifc_hlevel_derived_batch: nx*ny must be a multiple of 4 (use the per-field operators otherwise)"
+    levels = "mifc_hlevel_derived_levels: nx*ny must be a multiple of 4 (use the per-field operators otherwise)"
+    refused(batch, ctx.hlevel_derived_batch, t7, t7, t7, t7, ps7, al, bl, temp=("", 3), out={"ff": q7, "temp": q7})
+    refused(batch, ctx.hlevel_derived_batch, t7, t7, t7, t7, ps7, al, bl, temp=("", 3), out={"ff": q7, "temp": q7}, enqueue_counts=cnt5)
+    refused(batch, ctx.hlevel_derived_levels, t7, t7, t7, t7, ps7, al, bl, out={"ff": q7, "rh": q7, "theta": q7})
+    refused(levels, ctx.hlevel_derived_levels_enqueue, t7, t7, t7, t7, ps7, al, bl, q7, q7, q7, cnt5)
+    assert bool((q7 == 777.0).all())
+    dt, dps = torch.full_like(du, 280.0), torch.full((ny, nx), 1000.0, device="cuda")
+    for how in ({}, {"enqueue_counts": cnt5}):
+        refused("mifc_hlevel_derived_batch: temp_compute must be 1..5",
+                ctx.hlevel_derived_batch, du, dv, dt, dt, dps, al, bl, temp=("", 6), out={"ff": o0, "temp": o1}, **how)
+    assert all(bool((o == 777.0).all()) for o in (o0, o1, o2))
+
+
 @pytest.mark.parametrize("tiny", ["some", "all", "none"])
 def test_gradients_with_map_factors_whose_halves_are_inexact(gpu_ctx, oracle, tiny, mifc_env):
     """(float)(0.5 * m * d) of the one-sided gradients (FieldCalculations.cc:2015, :2027, :2040): the level-walking kernels

@@ -1,6 +1,6 @@
 // hostpath_probe.cc -- what the legacy host-pointer path can
 // get out of the host <-> HBM link on the box it runs on.  Prints one line per
-// measurement; the numbers pick the staging strategy in mifc_capi.hip.
+// measurement; the numbers pick the staging strategy in mifc_ctx.hip.
 //
 //   hipcc -O2 -o hostpath_probe hostpath_probe.cc -lpthread && ./hostpath_probe [MiB]
 #include <hip/hip_runtime.h>

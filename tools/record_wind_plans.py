@@ -113,7 +113,7 @@ def request_of(c):
     # arrays of their own, 256-byte aligned, levels nx * ny floats apart: only the width makes rows start off 16-byte boundaries
     rq["ragged"] = int(nx % 4 != 0 or (nlev > 1 and (nx * c["ny_global"]) % 4 != 0))
     rq["all_defined"] = int(every_all)
-    # the context's buffer for per-workgroup counts (stencil_partials in csrc/mifc_capi.hip); the slab and the three-output entries pass none
+    # the context's buffer for per-workgroup counts (stencil_partials in csrc/mifc_capi_stencil.hip); the slab and the three-output entries pass none
     per_level = (c["ny_local"] // 4 + 2) * (nx // 256 + 1)
     units = per_level * nlev
     has = (not every_all) and not slab and op != "vortdiv_ff" and per_level >= 2048 and units <= (1 << 24)
