@@ -196,6 +196,33 @@ def _level_batches(fields):
     return one, batches, fa, shape
 
 
+def _member_batch(fields, fdefined_in, fallback):
+    """What ensembleQuantiles and ensembleStatistics take alike: `fields` and `fdefined_in` as their docstrings say; fallback: the
+    member shape taken from the output, for a call without members, or None.  Returns (the members, their _Arg, shape, nlev,
+    ny, nx, the pointer table, the (nmem, nlev) int32 flags or None)."""
+    members = [fields[j] for j in range(fields.shape[0])] if isinstance(fields, np.ndarray) or _is_torch(fields) else list(fields)
+    fa = [_Arg(m) for m in members]
+    if fa:
+        shape = tuple(fa[0].shape)
+    elif fallback is not None:
+        shape = tuple(fallback)
+    else:
+        raise ValueError("no member fields and no output to take the shape from")
+    if len(shape) not in (2, 3):
+        raise ValueError("members must be (ny, nx) or (nlev, ny, nx) fields")
+    if not _same_shape(fa, shape):
+        raise ValueError("every member must have the shape %s" % (shape,))
+    nlev = shape[0] if len(shape) == 3 else 1
+    table = (ctypes.c_void_p * max(len(fa), 1))(*[a.addr for a in fa])
+    flags = None
+    if fdefined_in is not None:
+        f = np.asarray(fdefined_in, dtype=np.int32)
+        if f.ndim == 1:
+            f = np.repeat(f[:, None], nlev, axis=1)
+        flags = np.ascontiguousarray(f.reshape(len(fa), nlev), dtype=np.int32)
+    return members, fa, shape, nlev, shape[-2], shape[-1], table, flags
+
+
 def _level_coord(coord, hybrid, shape):
     """The coordinate argument: ps (ny, nx) of the hybrid form, else a batch like the fields."""
     ca = _Arg(coord)
@@ -654,22 +681,10 @@ class Context:
         themselves.  Returns (out, fdefined): an int for 2-D members, an int32 array of nlev flags otherwise.  A refused
         call raises RuntimeError with the reason."""
         code = {"lower": 0, "linear": 1}.get(method, -1) if isinstance(method, str) else int(method)
-        members = [fields[j] for j in range(fields.shape[0])] if isinstance(fields, np.ndarray) or _is_torch(fields) else list(fields)
         pct = np.ascontiguousarray(np.asarray(percentiles, dtype=np.float32).ravel())
         nq = int(pct.size)
-        fa = [_Arg(m) for m in members]
-        if fa:
-            shape = tuple(fa[0].shape)
-        elif out is not None:
-            shape = tuple(_Arg(out, output=True).shape)[1:]
-        else:
-            raise ValueError("no member fields and no output to take the shape from")
-        if len(shape) not in (2, 3):
-            raise ValueError("members must be (ny, nx) or (nlev, ny, nx) fields")
-        if not _same_shape(fa, shape):
-            raise ValueError("every member must have the shape %s" % (shape,))
-        nlev = shape[0] if len(shape) == 3 else 1
-        ny, nx = shape[-2], shape[-1]
+        fallback = None if out is None else tuple(_Arg(out, output=True).shape)[1:]
+        members, fa, shape, nlev, ny, nx, table, flags = _member_batch(fields, fdefined_in, fallback)
         if out is None:
             out = _empty_like(members[0], (nq,) + shape)
         oa = _Arg(out, output=True)
@@ -678,14 +693,7 @@ class Context:
         mk = _memkind(fa + [oa], self.device)
         self._bind_stream(mk)
         level_bytes = nlev * ny * nx * 4
-        table = (ctypes.c_void_p * max(len(fa), 1))(*[a.addr for a in fa])
         outs = (ctypes.c_void_p * max(nq, 1))(*[oa.addr + q * level_bytes for q in range(nq)])
-        flags = None
-        if fdefined_in is not None:
-            f = np.asarray(fdefined_in, dtype=np.int32)
-            if f.ndim == 1:
-                f = np.repeat(f[:, None], nlev, axis=1)
-            flags = np.ascontiguousarray(f.reshape(len(fa), nlev), dtype=np.int32)
         fd = np.zeros(nlev, np.int32)
         if not self._call("mifc_ensembleQuantiles", [code, nx, ny, nlev, ctypes.addressof(table), flags, len(fa), pct, nq, ctypes.addressof(outs), fd,
                                                       float(undef), mk]):
@@ -881,24 +889,12 @@ class Context:
         sequence of one per product.  Returns a list of (array, flags) in product order: flags an int for 2-D members,
         an int32 array of nlev flags otherwise.  A refused call raises RuntimeError with the reason."""
         specs = ensemble_products(products)
-        members = [fields[j] for j in range(fields.shape[0])] if isinstance(fields, np.ndarray) or _is_torch(fields) else list(fields)
-        fa = [_Arg(m) for m in members]
         if out is not None and (isinstance(out, np.ndarray) or _is_torch(out)):
             out = [out[k] for k in range(out.shape[0])]
         if out is not None and len(out) != len(specs):
             raise ValueError("out must hold one array per product")
-        if fa:
-            shape = tuple(fa[0].shape)
-        elif out is not None:
-            shape = tuple(_Arg(out[0], output=True).shape)
-        else:
-            raise ValueError("no member fields and no output to take the shape from")
-        if len(shape) not in (2, 3):
-            raise ValueError("members must be (ny, nx) or (nlev, ny, nx) fields")
-        if not _same_shape(fa, shape):
-            raise ValueError("every member must have the shape %s" % (shape,))
-        nlev = shape[0] if len(shape) == 3 else 1
-        ny, nx = shape[-2], shape[-1]
+        fallback = None if out is None else tuple(_Arg(out[0], output=True).shape)
+        members, fa, shape, nlev, ny, nx, table, flags = _member_batch(fields, fdefined_in, fallback)
         if out is None:
             out = [_empty_like(members[0], shape) for _ in specs]
         oa = [_Arg(o, output=True) for o in out]
@@ -906,13 +902,6 @@ class Context:
             raise ValueError("every output must have the shape %s" % (shape,))
         mk = _memkind(fa + oa, self.device)
         self._bind_stream(mk)
-        table = (ctypes.c_void_p * max(len(fa), 1))(*[a.addr for a in fa])
-        flags = None
-        if fdefined_in is not None:
-            f = np.asarray(fdefined_in, dtype=np.int32)
-            if f.ndim == 1:
-                f = np.repeat(f[:, None], nlev, axis=1)
-            flags = np.ascontiguousarray(f.reshape(len(fa), nlev), dtype=np.int32)
         fds = []
         prods = (_capi.EnsProduct * len(specs))()
         for k, (stat, compute, limits, flag_in) in enumerate(specs):

@@ -188,20 +188,6 @@ inline size_t align_up(size_t bytes, size_t pow2)
   return (bytes + pow2 - 1) & ~(pow2 - 1);
 }
 
-// Bounded staging of a host-memory ensemble batch (mifc_ensembleQuantiles, mifc_ensemble_levels): `per_cell` bytes of
-// device memory per staged cell, `budget` bytes in all.  Whole levels while they fit, else a range of cells of one level.
-inline void plan_level_chunks(size_t budget, size_t cells, size_t per_cell, size_t nlev, size_t* lev_chunk, size_t* cell_chunk)
-{
-  *lev_chunk = nlev;
-  *cell_chunk = cells;
-  if (cells * per_cell <= budget) {
-    *lev_chunk = nlev < budget / (cells * per_cell) ? nlev : budget / (cells * per_cell);
-  } else {
-    *lev_chunk = 1;
-    *cell_chunk = budget / per_cell > 1 ? budget / per_cell : 1;
-  }
-}
-
 // Do [a, a + abytes) and [b, b + bbytes) share a byte?  (Two empty ranges never do, not even at the same address.)
 inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes)
 {

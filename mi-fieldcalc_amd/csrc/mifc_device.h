@@ -644,6 +644,19 @@ __device__ __forceinline__ void block_count_add(u64* counter, unsigned int my_co
   block_count_add<1>(c, n);
 }
 
+// Member batches (mifc_quantile.hip, mifc_ensemble_levels.hip): the member pointers and the per-level ALL_DEFINED member
+// bits travel in the kernel arguments while they fit and in a device table beyond.  Params: QuantileParams, EnsLevelsParams.
+template <class Params>
+__device__ __forceinline__ const float* arg_mem(const Params& P, int j)
+{
+  return P.inline_args ? P.mem_inline[j] : P.tab.mem[j];
+}
+template <class Params>
+__device__ __forceinline__ u64 arg_all(const Params& P, int lev, int w)
+{
+  return P.inline_args ? P.all_inline[lev] : P.tab.all_bits[(long)lev * P.words + w];
+}
+
 } // namespace mifc
 
 #endif // MIFC_DEVICE_H

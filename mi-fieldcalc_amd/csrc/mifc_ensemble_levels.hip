@@ -21,14 +21,6 @@ namespace {
 
 constexpr int MB = 8; // members per group of loads
 
-__device__ __forceinline__ const float* lv_mem(const EnsLevelsParams& P, int j)
-{
-  return P.inline_args ? P.mem_inline[j] : P.tab.mem[j];
-}
-__device__ __forceinline__ u64 lv_all(const EnsLevelsParams& P, int lev, int w)
-{
-  return P.inline_args ? P.all_inline[lev] : P.tab.all_bits[(long)lev * P.words + w];
-}
 __device__ __forceinline__ u64 lv_none(const EnsLevelsParams& P, int lev, int w)
 {
   return P.inline_args ? P.none_inline[lev] : P.tab.none_bits[(long)lev * P.words + w];
@@ -234,8 +226,8 @@ __global__ __launch_bounds__(256) void ensemble_levels_kernel(const EnsLevelsPar
         float v[MB][C];
 #pragma unroll
         for (int k = 0; k < MB; ++k)
-          lv_load<C>(lv_mem(P, j0 + k < P.nmem ? j0 + k : P.nmem - 1), at, v[k]);
-        const u64 all_w = lv_all(P, lev, j0 >> 6) >> (j0 & 63), none_w = NP > 0 ? lv_none(P, lev, j0 >> 6) >> (j0 & 63) : 0ull;
+          lv_load<C>(arg_mem(P, j0 + k < P.nmem ? j0 + k : P.nmem - 1), at, v[k]);
+        const u64 all_w = arg_all(P, lev, j0 >> 6) >> (j0 & 63), none_w = NP > 0 ? lv_none(P, lev, j0 >> 6) >> (j0 & 63) : 0ull;
 #pragma unroll
         for (int k = 0; k < MB; ++k)
           if (j0 + k < P.nmem)

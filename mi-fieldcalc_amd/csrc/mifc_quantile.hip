@@ -34,10 +34,6 @@ __device__ __forceinline__ float q_unkey(unsigned k) // 0xffffffff -> 0x7fffffff
   return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
-__device__ __forceinline__ const float* q_mem(const QuantileParams& P, int j)
-{
-  return P.inline_args ? P.mem_inline[j] : P.tab.mem[j];
-}
 __device__ __forceinline__ float* q_out(const QuantileParams& P, int q)
 {
   return P.inline_args ? P.out_inline[q] : P.tab.out[q];
@@ -45,10 +41,6 @@ __device__ __forceinline__ float* q_out(const QuantileParams& P, int q)
 __device__ __forceinline__ float q_p(const QuantileParams& P, int q)
 {
   return P.inline_args ? P.p_inline[q] : P.tab.p[q];
-}
-__device__ __forceinline__ u64 q_all(const QuantileParams& P, int lev, int w)
-{
-  return P.inline_args ? P.all_inline[lev] : P.tab.all_bits[(long)lev * P.words + w];
 }
 
 // Batcher's odd-even merge sort on K keys, as a comparator list built at compile time
@@ -136,8 +128,8 @@ struct SortedRank
 
 __device__ __forceinline__ unsigned q_member_key(const QuantileParams& P, int lev, int j, long at, bool& def)
 {
-  const float x = q_mem(P, j)[at];
-  def = ((q_all(P, lev, j >> 6) >> (j & 63)) & 1ull) || is_def(x, P.undef);
+  const float x = arg_mem(P, j)[at];
+  def = ((arg_all(P, lev, j >> 6) >> (j & 63)) & 1ull) || is_def(x, P.undef);
   return def ? q_key(x) : 0xffffffffu;
 }
 
@@ -200,7 +192,7 @@ template <int K>
 __global__ __launch_bounds__(256) void quantile_sort_kernel(const QuantileParams P)
 {
   for (int l = blockIdx.y; l < P.nlev; l += gridDim.y) { // uniform per workgroup
-    const u64 all = q_all(P, P.lev0 + l, 0);
+    const u64 all = arg_all(P, P.lev0 + l, 0);
     unsigned int bad = 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < P.n; i += (long)gridDim.x * 256) {
       const long at = (long)l * P.stride + i;
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(256) void quantile_sort_kernel(const QuantileParams
       if (P.nmem > 0) {
 #pragma unroll
         for (int j = 0; j < K; ++j)
-          x[j] = q_mem(P, j < P.nmem ? j : 0)[at];
+          x[j] = arg_mem(P, j < P.nmem ? j : 0)[at];
       } else {
 #pragma unroll
         for (int j = 0; j < K; ++j)

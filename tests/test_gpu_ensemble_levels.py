@@ -200,6 +200,36 @@ def test_host_batches_in_several_chunks(gpu_ctx, oracle, mifc_env):
         check(gpu_ctx, oracle, x, mixed_flags(nmem, nlev, nlev), with_flags(products, nlev, nmem), device=False, label=("chunks", nmem, nlev))
 
 
+# The seams of the chunk plan at the smallest shapes that reach them.  The budget is 1 MiB = 1 048 576 bytes, a staged cell
+# costs 4 * (nmem + 4 products) bytes: 256 with 60 members (4 096 cells per MiB), 252 with 59 (4 161).
+CHUNK_SEAMS = {
+    "a level fits exactly": (60, 3, 64, 64, False),        # 4 096 cells: one level per chunk, no cell split
+    "one cell over": (60, 2, 17, 241, False),              # 4 097 cells: ranges of 4 096 and 1
+    "a short last chunk of levels": (60, 6, 25, 40, False),  # four levels per chunk: 4 + 2
+    "ranges cut at a multiple of 4": (59, 1, 25, 333, False),  # 8 325 cells: 4 161 rounded to 4 160 / 4 160 / 5
+    "no members": (0, 2, 6, 8, False),                     # no scratch for members; the flags of `mean`
+    "device table, host": (9, 70, 6, 8, False),            # past the 64 levels of the kernel arguments
+    "device table, device": (9, 70, 6, 8, True),
+}
+
+
+@pytest.mark.parametrize("case", list(CHUNK_SEAMS))
+def test_chunk_seams(gpu_ctx, oracle, mifc_env, case):
+    mifc_env("MIFC_ENSEMBLE_CHUNK_MIB", 1)
+    nmem, nlev, ny, nx, device = CHUNK_SEAMS[case]
+    four = ["mean", "stddev", "max", ("probability", 1, [0.5])]
+    x = make_members(nmem, nlev, ny, nx, 7 * nmem + nlev)
+    flags = mixed_flags(nmem, nlev, nlev)
+    if nmem > 0:
+        check(gpu_ctx, oracle, x, flags, with_flags(four, nlev, nmem), device=device, label=case)
+        return
+    four = ["mean", "stddev", ("sum", np.full(nlev, SOME_DEFINED, np.int32)), ("probability", 1, [0.5])]  # (no extreme without members)
+    res = gpu_ctx.ensembleStatistics([], four, out=np.full((4, nlev, ny, nx), -7.0, np.float32))  # the shape comes from the output
+    for (got, fd), p in zip(res, four):
+        exp, efd = expected(oracle, x, flags, p)
+        assert same_bits(got, exp) and list(fd) == efd, p
+
+
 def test_big_level_counts_through_partials(gpu_ctx, oracle):
     """2 048 workgroups per level and more: the undefined counts go through the per-workgroup table."""
     nmem, nlev, ny, nx = 3, 2, 1100, 2048
@@ -229,7 +259,7 @@ def test_refusals_write_nothing(gpu_ctx):
         return dict(stat=stat, compute=compute, limits=limits, out=outs[k].data_ptr() if out is True else out,
                     fd=fds[k].ctypes.data if fd else None)
 
-    def call(products, nx_=nx, ny_=ny, nlev_=nlev, nmem_=nmem, fields=None, nproducts=None, null_products=False, sync=True):
+    def call(products, nx_=nx, ny_=ny, nlev_=nlev, nmem_=nmem, fields=None, nproducts=None, null_products=False, memkind=1, sync=True):
         tab = (ctypes.c_void_p * nmem)(*[x[j].data_ptr() for j in range(nmem)]) if fields is None or fields == "null" else fields
         arr = (capi.EnsProduct * max(len(products), 1))()
         for k, p in enumerate(products):
@@ -239,53 +269,58 @@ def test_refusals_write_nothing(gpu_ctx):
             arr[k].out, arr[k].fdefined = p["out"], p["fd"]
         rc = lib.mifc_ensemble_levels(c, nx_, ny_, nlev_, None if fields == "null" else ctypes.addressof(tab), None, nmem_,
                                       None if null_products else ctypes.addressof(arr), len(products) if nproducts is None else nproducts,
-                                      float(UNDEF), 1)
+                                      float(UNDEF), memkind)
         if sync:
             torch.cuda.synchronize()
         return rc, gpu_ctx.last_error()
 
     SUM, MEAN, STD, EXT, PROB = 0, 1, 2, 3, 4
     mean = [product(0, MEAN)]
-    cases = {
-        "nproducts < 1": dict(products=mean, nproducts=0),
-        "sixteen products": dict(products=[product(k, PROB, 1) for k in range(16)]),
-        "nine probabilities": dict(products=[product(k, PROB, 1 + k % 6, (0.0, 1.0)) for k in range(9)]),
-        "two means": dict(products=[product(0, MEAN), product(1, MEAN)]),
-        "two sums": dict(products=[product(0, SUM), product(1, STD), product(2, SUM)]),
-        "two max": dict(products=[product(0, EXT, 1), product(1, EXT, 1)]),
-        "unknown stat": dict(products=[product(0, 5)]),
-        "negative stat": dict(products=[product(0, -1)]),
-        "extreme compute 0": dict(products=[product(0, EXT, 0)]),
-        "extreme compute 5": dict(products=[product(0, EXT, 5)]),
-        "probability compute 0": dict(products=[product(0, PROB, 0)]),
-        "probability compute 7": dict(products=[product(0, PROB, 7)]),
-        "probability nlimits 0": dict(products=[product(0, PROB, 1, ())]),
-        "probability nlimits 3": dict(products=[product(0, PROB, 1, (0.0, 1.0, 2.0))]),
-        "between with one limit (3)": dict(products=[product(0, PROB, 3)]),
-        "between with one limit (6)": dict(products=[product(0, MEAN), product(1, PROB, 6)]),
-        "extreme without members": dict(products=[product(0, EXT, 2)], nmem_=0),
-        "nlev < 1": dict(products=mean, nlev_=0),
-        "negative nx": dict(products=mean, nx_=-1),
-        "negative ny": dict(products=mean, ny_=-3),
-        "negative nmem": dict(products=mean, nmem_=-1),
-        "null products": dict(products=mean, null_products=True),
-        "null fields": dict(products=mean, fields="null"),
-        "null member": dict(products=mean, fields=(ctypes.c_void_p * nmem)(*([x[0].data_ptr()] * (nmem - 1) + [None]))),
-        "null output": dict(products=[product(0, MEAN), product(1, STD, out=None)]),
-        "null flags": dict(products=[product(0, MEAN), product(1, STD, fd=False)]),
-        "same output twice": dict(products=[product(0, MEAN), product(0, STD)]),
-        "outputs overlap": dict(products=[product(0, MEAN), product(1, STD, out=outs[0].data_ptr() + 4 * ny * nx)]),
-        "output is a member": dict(products=[product(0, MEAN), product(1, STD, out=x[3].data_ptr())]),
-        "output overlaps a member": dict(products=[product(0, MEAN, out=x[1].data_ptr() + 16)]),
+    held, shape, null = ": the list holds this statistic already", "nlev < 1, or a negative nx, ny or nmem", "a null pointer (products or fields)"
+    between = ": PROBABILITY between two limits with one limit (the reference returns false)"
+    cases = {  # what: (the call, the text behind "mifc_ensemble_levels: ")
+        "nproducts < 1": (dict(products=mean, nproducts=0), "nproducts < 1"),
+        "sixteen products": (dict(products=[product(k, PROB, 1) for k in range(16)]), "more than 15 products"),
+        "nine probabilities": (dict(products=[product(k, PROB, 1 + k % 6, (0.0, 1.0)) for k in range(9)]), "more than 8 PROBABILITY products"),
+        "two means": (dict(products=[product(0, MEAN), product(1, MEAN)]), "products[1]" + held),
+        "two sums": (dict(products=[product(0, SUM), product(1, STD), product(2, SUM)]), "products[2]" + held),
+        "two max": (dict(products=[product(0, EXT, 1), product(1, EXT, 1)]), "products[1]" + held),
+        "unknown stat": (dict(products=[product(0, 5)]), "products[0]: unknown stat 5"),
+        "negative stat": (dict(products=[product(0, -1)]), "products[0]: unknown stat -1"),
+        "extreme compute 0": (dict(products=[product(0, EXT, 0)]), "products[0]: EXTREME compute 0 outside 1..4"),
+        "extreme compute 5": (dict(products=[product(0, EXT, 5)]), "products[0]: EXTREME compute 5 outside 1..4"),
+        "probability compute 0": (dict(products=[product(0, PROB, 0)]), "products[0]: PROBABILITY compute 0 outside 1..6"),
+        "probability compute 7": (dict(products=[product(0, PROB, 7)]), "products[0]: PROBABILITY compute 7 outside 1..6"),
+        "probability nlimits 0": (dict(products=[product(0, PROB, 1, ())]), "products[0]: PROBABILITY nlimits 0 outside 1..2"),
+        "probability nlimits 3": (dict(products=[product(0, PROB, 1, (0.0, 1.0, 2.0))]), "products[0]: PROBABILITY nlimits 3 outside 1..2"),
+        "between with one limit (3)": (dict(products=[product(0, PROB, 3)]), "products[0]" + between),
+        "between with one limit (6)": (dict(products=[product(0, MEAN), product(1, PROB, 6)]), "products[1]" + between),
+        "extreme without members": (dict(products=[product(0, EXT, 2)], nmem_=0), "products[0]: EXTREME without members (the reference returns false)"),
+        "nlev < 1": (dict(products=mean, nlev_=0), shape),
+        "negative nx": (dict(products=mean, nx_=-1), shape),
+        "negative ny": (dict(products=mean, ny_=-3), shape),
+        "negative nmem": (dict(products=mean, nmem_=-1), shape),
+        "unknown memkind": (dict(products=mean, memkind=7), "unknown memkind 7"),
+        "null products": (dict(products=mean, null_products=True), null),
+        "null fields": (dict(products=mean, fields="null"), null),
+        "null member": (dict(products=mean, fields=(ctypes.c_void_p * nmem)(*([x[0].data_ptr()] * (nmem - 1) + [None]))), "a null pointer (fields[4])"),
+        "null output": (dict(products=[product(0, MEAN), product(1, STD, out=None)]), "a null pointer (products[1].out or .fdefined)"),
+        "null flags": (dict(products=[product(0, MEAN), product(1, STD, fd=False)]), "a null pointer (products[1].out or .fdefined)"),
+        "more than 2^31 - 1 cells": (dict(products=mean, nx_=46341, ny_=46341), "more than 2^31 - 1 cells per level"),
+        "same output twice": (dict(products=[product(0, MEAN), product(0, STD)]), "two outputs are the same array or overlap"),
+        "outputs overlap": (dict(products=[product(0, MEAN), product(1, STD, out=outs[0].data_ptr() + 4 * ny * nx)]),
+                            "two outputs are the same array or overlap"),
+        "output is a member": (dict(products=[product(0, MEAN), product(1, STD, out=x[3].data_ptr())]), "products[1].out overlaps fields[3]"),
+        "output overlaps a member": (dict(products=[product(0, MEAN, out=x[1].data_ptr() + 16)]), "products[0].out overlaps fields[1]"),
     }
     before = x.clone()
 
     def untouched():  # the members hold NaN, so their bits are compared
         return (outs == sentinel).all().item() and (fds == 7).all() and torch.equal(x.view(torch.int32), before.view(torch.int32))
 
-    for what, kw in cases.items():
+    for what, (kw, text) in cases.items():
         rc, err = call(**kw)
-        assert rc == 0 and err.startswith("mifc_ensemble_levels: "), (what, rc, err)
+        assert rc == 0 and err == "mifc_ensemble_levels: " + text, (what, rc, err)
         assert untouched(), what
     with pytest.raises(ValueError):
         gpu_ctx.ensembleStatistics(x, ["median"])

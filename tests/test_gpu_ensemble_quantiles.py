@@ -123,6 +123,35 @@ def test_host_batches_in_several_chunks(gpu_ctx, mifc_env):
         check(gpu_ctx, x[:, :1], [50], "lower", flags[:, :1], device=False, label=("chunks", nmem, 1))
 
 
+# The seams of the chunk plan at the smallest shapes that reach them.  The budget is 1 MiB = 1 048 576 bytes, a staged cell
+# costs 4 * (nmem + 4 percentiles) bytes: 256 with 60 members (4 096 cells per MiB), 252 with 59 (4 161).
+CHUNK_SEAMS = {
+    "a level fits exactly": (60, 3, 64, 64, False),        # 4 096 cells: one level per chunk, no cell split
+    "one cell over": (60, 2, 17, 241, False),              # 4 097 cells: ranges of 4 096 and 1
+    "a short last chunk of levels": (60, 6, 25, 40, False),  # four levels per chunk: 4 + 2
+    "ranges off the multiple of 4": (59, 1, 25, 333, False),  # 8 325 cells: 4 161 / 4 161 / 3 (no rounding here)
+    "no members": (0, 2, 6, 8, False),                     # no scratch for members; NONE_DEFINED
+    "device table, host": (9, 70, 6, 8, False),            # past the 64 levels of the kernel arguments
+    "device table, device": (9, 70, 6, 8, True),
+}
+
+
+@pytest.mark.parametrize("case", list(CHUNK_SEAMS))
+def test_chunk_seams(gpu_ctx, mifc_env, case):
+    mifc_env("MIFC_QUANTILE_CHUNK_MIB", 1)
+    nmem, nlev, ny, nx, device = CHUNK_SEAMS[case]
+    ps = [10, 37.5, 50, 90]
+    x = make_members(nmem, nlev, ny, nx, 7 * nmem + nlev)
+    flags = mixed_flags(nmem, nlev, nlev)
+    if nmem > 0:
+        check(gpu_ctx, x, ps, "linear", flags, device=device, label=case)
+        return
+    out = np.full((4, nlev, ny, nx), -7.0, np.float32)  # the shape comes from the output
+    got, fd = gpu_ctx.ensembleQuantiles([], ps, method="linear", out=out)
+    exp, efd = qr.quantiles(x, ps, qr.LINEAR, flags)
+    assert same_bits(got, exp) and list(fd) == efd == [qr.NONE_DEFINED] * nlev
+
+
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
 @pytest.mark.parametrize("nmem", [51, 70])
 def test_output_aliasing_members(gpu_ctx, device, nmem):
@@ -148,37 +177,46 @@ def test_refusals_write_nothing(gpu_ctx):
     sentinel = -4242.5
     outs = torch.full((3, nlev, ny, nx), sentinel, dtype=torch.float32, device="cuda")
 
-    def call(method=0, nx_=nx, ny_=ny, nlev_=nlev, nmem_=nmem, ps=(10.0, 50.0, 90.0), nq=3, out_ptrs=None, fields=None, fd_out=True, sync=True):
-        tab = (ctypes.c_void_p * nmem)(*[x[j].data_ptr() for j in range(nmem)]) if fields is None else fields
-        o = (ctypes.c_void_p * 3)(*(out_ptrs or [outs[q].data_ptr() for q in range(3)]))
-        p = np.asarray(ps, np.float32)
+    def call(method=0, nx_=nx, ny_=ny, nlev_=nlev, nmem_=nmem, ps=(10.0, 50.0, 90.0), nq=3, out_ptrs=None, fields=None, fd_out=True, memkind=1,
+             sync=True):
+        tab = (ctypes.c_void_p * nmem)(*[x[j].data_ptr() for j in range(nmem)]) if fields is None or fields == "null" else fields
+        o = (ctypes.c_void_p * 3)(*([outs[q].data_ptr() for q in range(3)] if out_ptrs is None or out_ptrs == "null" else out_ptrs))
+        p = np.asarray((0.0,) if ps is None else ps, np.float32)
         fd = np.full(nlev, 7, np.int32)
-        rc = lib.mifc_ensembleQuantiles(c, method, nx_, ny_, nlev_, ctypes.addressof(tab), None, nmem_, p.ctypes.data, nq, ctypes.addressof(o),
-                                        fd.ctypes.data if fd_out else None, float(qr.UNDEF), 1)
+        rc = lib.mifc_ensembleQuantiles(c, method, nx_, ny_, nlev_, None if fields == "null" else ctypes.addressof(tab), None, nmem_,
+                                        None if ps is None else p.ctypes.data, nq, None if out_ptrs == "null" else ctypes.addressof(o),
+                                        fd.ctypes.data if fd_out else None, float(qr.UNDEF), memkind)
         if sync:
             torch.cuda.synchronize()
         return rc, gpu_ctx.last_error(), fd
 
     nan = float("nan")
-    cases = {
-        "unknown method": dict(method=2),
-        "negative method": dict(method=-1),
-        "nq < 1": dict(nq=0),
-        "NaN percentile": dict(ps=(10.0, nan, 90.0)),
-        "percentile < 0": dict(ps=(-0.5, 50.0, 90.0)),
-        "percentile > 100": dict(ps=(10.0, 50.0, 100.5)),
-        "nlev < 1": dict(nlev_=0),
-        "negative nx": dict(nx_=-1),
-        "negative ny": dict(ny_=-3),
-        "negative nmem": dict(nmem_=-1),
-        "null member": dict(fields=(ctypes.c_void_p * nmem)(*([x[0].data_ptr()] * (nmem - 1) + [None]))),
-        "null output": dict(out_ptrs=[outs[0].data_ptr(), None, outs[2].data_ptr()]),
-        "null flags out": dict(fd_out=False),
-        "same output twice": dict(out_ptrs=[outs[0].data_ptr(), outs[1].data_ptr(), outs[0].data_ptr()]),
+    shape = "nlev < 1, or a negative nx, ny or nmem"
+    null = "a null pointer (percentiles, fres, fdefined_out or fields)"
+    cases = {  # what: (the call, the text behind "mifc_ensembleQuantiles: ")
+        "unknown method": (dict(method=2), "unknown method 2 (MIFC_QUANTILE_LOWER or MIFC_QUANTILE_LINEAR)"),
+        "negative method": (dict(method=-1), "unknown method -1 (MIFC_QUANTILE_LOWER or MIFC_QUANTILE_LINEAR)"),
+        "nq < 1": (dict(nq=0), "nq < 1"),
+        "NaN percentile": (dict(ps=(10.0, nan, 90.0)), "percentiles[1] is NaN or outside [0, 100]"),
+        "percentile < 0": (dict(ps=(-0.5, 50.0, 90.0)), "percentiles[0] is NaN or outside [0, 100]"),
+        "percentile > 100": (dict(ps=(10.0, 50.0, 100.5)), "percentiles[2] is NaN or outside [0, 100]"),
+        "nlev < 1": (dict(nlev_=0), shape),
+        "negative nx": (dict(nx_=-1), shape),
+        "negative ny": (dict(ny_=-3), shape),
+        "negative nmem": (dict(nmem_=-1), shape),
+        "unknown memkind": (dict(memkind=7), "unknown memkind 7"),
+        "null fields": (dict(fields="null"), null),
+        "null percentiles": (dict(ps=None), null),
+        "null fres": (dict(out_ptrs="null"), null),
+        "null member": (dict(fields=(ctypes.c_void_p * nmem)(*([x[0].data_ptr()] * (nmem - 1) + [None]))), "a null pointer (fields[4])"),
+        "null output": (dict(out_ptrs=[outs[0].data_ptr(), None, outs[2].data_ptr()]), "a null pointer (fres[1])"),
+        "null flags out": (dict(fd_out=False), null),
+        "more than 2^31 - 1 cells": (dict(nx_=46341, ny_=46341), "more than 2^31 - 1 cells per level"),
+        "same output twice": (dict(out_ptrs=[outs[0].data_ptr(), outs[1].data_ptr(), outs[0].data_ptr()]), "two outputs are the same array or overlap"),
     }
-    for what, kw in cases.items():
+    for what, (kw, text) in cases.items():
         rc, err, fd = call(**kw)
-        assert rc == 0 and err.startswith("mifc_ensembleQuantiles: "), (what, err)
+        assert rc == 0 and err == "mifc_ensembleQuantiles: " + text, (what, err)
         assert (outs == sentinel).all().item() and (fd == 7).all(), what
     with pytest.raises(RuntimeError, match="mifc_ensembleQuantiles"):
         gpu_ctx.ensembleQuantiles(x, [50], method="median")
