@@ -667,6 +667,17 @@ unsigned long long mifc_stencil_count_domain(int op, int nx, int ny);
  * and for the operators with launchers of their own.  The tests use it to check that a case reaches the kernel it is
  * meant for; nothing on the data path reads it.  The string is static. */
 const char* mifc_last_stencil_form(void);
+/* Diagnostic: the launch shape of the calling thread's last elementwise (vectorabs, *leveltemp, *levelhum, cvhum, momentum
+ * coordinates), catalogue (the other pointwise operators) or fused derived-batch launch, as "key=value" words:
+ *   family=ewise|pointwise|derived  op=<kernel instantiation>  form=vector|scalar (four cells per lane | one)
+ *   grid=<workgroups of 256 lanes; derived: per level>  partials=0|1 (the undefined counts went through the partials
+ *   buffer)  tail=<cells of the extra 64-lane launch>  n=<cells per field>
+ * and for family=derived also  nlev=<levels>  inst=ff+rh+theta|ff+rh+theta+td|rh+theta|rh+theta+td|ff|generic
+ * check=0|1 (per-cell tests compiled in)  pipe=0|1 (two-trip software pipeline).  A lane of the vector form makes
+ * ceil((n / 4) / (grid * 256)) trips at the most.  "" before the first such launch (and after a call that launched
+ * nothing the previous report stays).  For tests; nothing on the data path reads it.  The string is thread-local and
+ * overwritten by the next query. */
+const char* mifc_last_pointwise_form(void);
 
 /* The same plus the rest of the stencil family over a batch of levels, the map
  * and Coriolis fields shared by all levels:

@@ -1177,6 +1177,13 @@ class Context:
         """The kernel form this thread's last stencil launch took (mifc_last_stencil_form; a diagnostic for tests)."""
         return self._lib.mifc_last_stencil_form().decode()
 
+    def last_pointwise_form(self):
+        """The launch shape of this thread's last elementwise, catalogue or derived-batch launch as a dict
+        (mifc_last_pointwise_form; a diagnostic for tests): family, form, inst as strings, the other keys as ints."""
+        text = self._lib.mifc_last_pointwise_form().decode()
+        form = dict(word.split("=", 1) for word in text.split())
+        return {k: (v if k in ("family", "form", "inst") else int(v)) for k, v in form.items()}
+
     def stencil_count_domain(self, op, nx, ny):
         return int(self._lib.mifc_stencil_count_domain(self.OPS[op], nx, ny))
 

@@ -264,4 +264,9 @@ int mifc_momentumYcoordinate(mifc_ctx* c, int nx, int ny, const float* u, const 
   return momentum_coordinate(c, mifc::EW_MOMENTUM_Y, nx, ny, u, ymapr, fcoriolis, fcoriolisMin, nxy, fdefined, undef, memkind);
 }
 
+const char* mifc_last_pointwise_form(void)
+{
+  return mifc::last_pointwise_form();
+}
+
 } // extern "C"

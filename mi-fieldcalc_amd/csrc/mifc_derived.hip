@@ -261,27 +261,38 @@ __global__ __launch_bounds__(256) void derived_levels_kernel(const DerivedParams
 }
 
 template <bool CHECK>
-void launch_one(const DerivedParams& p, dim3 grid, hipStream_t stream)
+void launch_one(const DerivedParams& p, dim3 grid, hipStream_t stream, PointwiseForm& form)
 {
   const int hc = p.hum ? p.hum_code : 0, dc = p.td ? p.td_code : 0, tc = p.temp ? p.temp_compute : 0;
   const int rh = hum_code(HUM_Q_RH, 0), td = hum_code(HUM_Q_TD, 0);
   const bool ff = p.ff != nullptr;
   // the compile-time combinations: wind speed + RH + theta (BASELINE.json config 2), the same with the
   // dew point, and the two without the wind
-  if (tc == 3 && hc == rh && dc == 0 && ff && env().derived_pipe == 0)
+  form.check = CHECK ? 1 : 0;
+  form.pipe = 1;
+  if (tc == 3 && hc == rh && dc == 0 && ff && env().derived_pipe == 0) {
+    form.inst = "ff+rh+theta";
+    form.pipe = 0;
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 1, 3, 1 + HUM_Q_RH, 0, false>), grid, dim3(256), 0, stream, p);
-  else if (tc == 3 && hc == rh && dc == 0 && ff)
+  } else if (tc == 3 && hc == rh && dc == 0 && ff) {
+    form.inst = "ff+rh+theta";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 1, 3, 1 + HUM_Q_RH, 0>), grid, dim3(256), 0, stream, p);
-  else if (tc == 3 && hc == rh && dc == td && ff)
+  } else if (tc == 3 && hc == rh && dc == td && ff) {
+    form.inst = "ff+rh+theta+td";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 1, 3, 1 + HUM_Q_RH, 1 + HUM_Q_TD>), grid, dim3(256), 0, stream, p);
-  else if (tc == 3 && hc == rh && dc == 0 && !ff)
+  } else if (tc == 3 && hc == rh && dc == 0 && !ff) {
+    form.inst = "rh+theta";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 0, 3, 1 + HUM_Q_RH, 0>), grid, dim3(256), 0, stream, p);
-  else if (tc == 3 && hc == rh && dc == td && !ff)
+  } else if (tc == 3 && hc == rh && dc == td && !ff) {
+    form.inst = "rh+theta+td";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 0, 3, 1 + HUM_Q_RH, 1 + HUM_Q_TD>), grid, dim3(256), 0, stream, p);
-  else if (tc == 0 && hc == 0 && dc == 0 && ff)
+  } else if (tc == 0 && hc == 0 && dc == 0 && ff) {
+    form.inst = "ff";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, 1, 0, 0, 0>), grid, dim3(256), 0, stream, p);
-  else
+  } else {
+    form.inst = "generic";
     hipLaunchKernelGGL((derived_levels_kernel<CHECK, -1, -1, -1, -1>), grid, dim3(256), 0, stream, p);
+  }
 }
 
 } // namespace
@@ -329,10 +340,17 @@ hipError_t launch_derived_levels(const DerivedParams& prm, hipStream_t stream)
     p.cnt_hum = prm.cnt_hum ? prm.cnt_hum + l0 : nullptr;
     p.cnt_td = prm.cnt_td ? prm.cnt_td + l0 : nullptr;
     p.cnt_dd = prm.cnt_dd ? prm.cnt_dd + l0 : nullptr;
+    PointwiseForm form;
+    form.family = "derived";
+    form.vec = 1;
+    form.grid = gx;
+    form.nlev = nl;
+    form.n = prm.n;
     if (prm.every_level_all_defined)
-      launch_one<false>(p, dim3(gx, nl), stream);
+      launch_one<false>(p, dim3(gx, nl), stream, form);
     else
-      launch_one<true>(p, dim3(gx, nl), stream);
+      launch_one<true>(p, dim3(gx, nl), stream, form);
+    note_pointwise_form(form);
   }
   return hipGetLastError();
 }

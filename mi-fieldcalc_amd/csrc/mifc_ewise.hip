@@ -8,6 +8,7 @@
 #include "mifc_device.h"
 #include "mifc_kernels.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 namespace mifc {
@@ -304,6 +305,10 @@ hipError_t launch_ewise_op(const EwiseParams& prm, hipStream_t stream)
 {
   const bool vec_ok = aligned16(prm.in0) && aligned16(prm.out) && (!prm.in1 || aligned16(prm.in1)) && (!prm.in2 || aligned16(prm.in2)) && prm.n >= 4;
   const int block = 256;
+  PointwiseForm form;
+  form.family = "ewise";
+  form.op = OP;
+  form.n = prm.n;
   if (vec_ok) {
     const int n4 = prm.n >> 2;
     // Table-free variants: one float4 per lane, workgroups in address order (the
@@ -335,6 +340,10 @@ hipError_t launch_ewise_op(const EwiseParams& prm, hipStream_t stream)
     if (by_partials)
       (void)launch_count_partials(prm.partials, grid, prm.n_undefined, stream);
     const int tail = prm.n - n4 * 4;
+    form.vec = 1;
+    form.grid = grid;
+    form.partials = by_partials ? 1 : 0;
+    form.tail = tail;
     if (tail > 0) {
       EwiseParams t = prm;
       t.partials = nullptr;
@@ -349,8 +358,10 @@ hipError_t launch_ewise_op(const EwiseParams& prm, hipStream_t stream)
   } else {
     EwiseParams q = prm;
     q.partials = nullptr;
-    hipLaunchKernelGGL((ewise_kernel<OP, false>), dim3(grid_for(prm.n, block, 256 * 16)), dim3(block), 0, stream, q);
+    form.grid = grid_for(prm.n, block, 256 * 16);
+    hipLaunchKernelGGL((ewise_kernel<OP, false>), dim3(form.grid), dim3(block), 0, stream, q);
   }
+  note_pointwise_form(form);
   return hipGetLastError();
 }
 
@@ -382,6 +393,26 @@ hipError_t launch_ewise(const EwiseParams& prm, hipStream_t stream)
   default:
     return hipErrorInvalidValue;
   }
+}
+
+namespace {
+thread_local PointwiseForm t_pointwise_form;
+thread_local char t_pointwise_text[192];
+} // namespace
+void note_pointwise_form(const PointwiseForm& form)
+{
+  t_pointwise_form = form;
+}
+const char* last_pointwise_form()
+{
+  const PointwiseForm& f = t_pointwise_form;
+  if (!f.family[0])
+    return "";
+  int k = std::snprintf(t_pointwise_text, sizeof t_pointwise_text, "family=%s op=%d form=%s grid=%d partials=%d tail=%d n=%d", f.family, f.op,
+                        f.vec ? "vector" : "scalar", f.grid, f.partials, f.tail, f.n);
+  if (f.nlev > 0 && k > 0 && (size_t)k < sizeof t_pointwise_text)
+    std::snprintf(t_pointwise_text + k, sizeof t_pointwise_text - (size_t)k, " nlev=%d inst=%s check=%d pipe=%d", f.nlev, f.inst, f.check, f.pipe);
+  return t_pointwise_text;
 }
 
 } // namespace mifc

@@ -505,6 +505,25 @@ constexpr int kPrepMaxLevels = 2048;
 // diagnostic for tests and bug reports (mifc_last_stencil_form), nothing reads it on the data path.
 void note_form(const char* form);
 const char* last_form();
+// The launch shape of the calling thread's last elementwise (mifc_ewise.hip), catalogue (mifc_pointwise.hip) or fused
+// derived (mifc_derived.hip) launch: the same kind of diagnostic (mifc_last_pointwise_form).  The launchers store this
+// small struct, host side, once per call; the text is only formatted when somebody asks for it.
+struct PointwiseForm
+{
+  const char* family = ""; // "ewise" | "pointwise" | "derived"; "" before the first launch
+  int op = 0;              // kernel instantiation: the EwiseOp / PwOp template argument (0 for derived)
+  int vec = 0;             // 1: four cells per lane (16-byte accesses), 0: one cell per lane
+  int grid = 0;            // workgroups of the main launch (derived: gx, workgroups per level)
+  int nlev = 0;            // derived: levels (grid.y), else 0
+  int partials = 0;        // 1: the counts went by the partials buffer and count_partials_kernel
+  int tail = 0;            // cells of the 64-lane tail launch (n % 4 in the vector form, else 0)
+  int n = 0;               // cells per field (derived: per level)
+  const char* inst = "";   // derived: "ff+rh+theta", "ff+rh+theta+td", "rh+theta", "rh+theta+td", "ff" or "generic"
+  int check = 0;           // derived: the CHECK instantiation (some level is not ALL_DEFINED)
+  int pipe = 0;            // derived: the two-trip software pipeline
+};
+void note_pointwise_form(const PointwiseForm& form);
+const char* last_pointwise_form();
 hipError_t launch_prep_levels(const unsigned char* host_flags, int nlev, unsigned char* d_flags, u64* d_counts, int n_counts, hipStream_t stream);
 
 // second-order Shapiro filter, FieldCalculations.cc:2076 (mifc_shapiro.hip)

@@ -602,6 +602,10 @@ hipError_t launch_pw(const PwParams& prm, hipStream_t stream)
     vec_ok = vec_ok && aligned16(prm.in[k]);
   const int block = 256;
   const int cap = 0x7fffffff; // one float4 per lane: table staging (where an operator needs it) runs under the load latency
+  PointwiseForm form;
+  form.family = "pointwise";
+  form.op = OP;
+  form.n = prm.n;
   if (vec_ok) {
     const int n4 = prm.n >> 2;
     int g = (n4 + block - 1) / block;
@@ -614,6 +618,10 @@ hipError_t launch_pw(const PwParams& prm, hipStream_t stream)
     if (by_partials)
       (void)launch_count_partials(prm.partials, g, prm.n_undefined, stream);
     const int tail = prm.n - n4 * 4;
+    form.vec = 1;
+    form.grid = g;
+    form.partials = by_partials ? 1 : 0;
+    form.tail = tail;
     if (tail > 0) {
       PwParams t = prm;
       t.partials = nullptr;
@@ -629,7 +637,9 @@ hipError_t launch_pw(const PwParams& prm, hipStream_t stream)
     PwParams q = prm;
     q.partials = nullptr;
     hipLaunchKernelGGL((pointwise_kernel<OP, false>), dim3(g), dim3(block), 0, stream, q);
+    form.grid = g;
   }
+  note_pointwise_form(form);
   return hipGetLastError();
 }
 

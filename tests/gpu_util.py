@@ -190,3 +190,19 @@ def check_form(ctx, expected=None, differs_from=None, what=None):
         assert got == expected, (what, got, expected)
     if differs_from is not None:
         assert got != differs_from, (what, got)
+
+
+def run_is_forced():
+    """True when the whole run is under a path-selecting MIFC_* switch: assertions about launch shapes stand aside."""
+    return bool(_FORCED_SWITCHES)
+
+
+def check_pointwise_form(ctx, what=None, **expected):
+    """Assert the launch shape of the last elementwise, catalogue or derived-batch launch (mifc_last_pointwise_form), key by
+    key, and return the report -- unless the run forces a path: then nothing is asserted and None comes back."""
+    if _FORCED_SWITCHES:
+        return None
+    got = ctx.last_pointwise_form()
+    for key, value in expected.items():
+        assert got.get(key) == value, (what, key, value, got)
+    return got
