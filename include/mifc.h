@@ -524,6 +524,63 @@ int mifc_vderiv_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
                        const float* levels /* HOST float[nlev] */, int method, float* const* fres, int* fdefined_out,
                        float* const* fmag, int* fdefined_mag, float undef, int memkind);
 
+/* ---- EXTENSION: level batches sampled at arbitrary points (regridding, cross-sections, soundings) ------------
+ * Not a miutil::fieldcalc function: the reference's callers take a field to a flight route, a section line, a list of
+ * stations or the grid of another projection on the host, level by level (their field class has an
+ * interpolate(npos, xpos, ypos, ...) with a nearest, a bilinear and a cubic method).  nfields fields of [nlev][ny][nx]
+ * and npos positions go in, fres[f] is [nlev][npos] -- itself a level batch of shape (nlev, 1, npos), which
+ * mifc_vinterp_*, mifc_vlayer_* and mifc_vderiv_* take unchanged: a vertical cross-section on pressure surfaces is this
+ * call on the fields and on the pressure batch (or ps), then mifc_vinterp_*.  Positions are in grid-index units: x = 0 is
+ * column 0, x = nx - 1 the last column.  Rotating vector components between projections is OUT OF SCOPE: the caller
+ * rotates u, v with field algebra (mifc_fieldOPERfield).  Per point p, field f and level k:
+ *   1. Position.  x = xpos[p], y = ypos[p].  The position is unusable if !is_defined(false, x, undef) or
+ *      !is_defined(false, y, undef) (NaN, or equal to undef), and, with xd = (double)x, yd = (double)y, unless
+ *      xd >= 0.0 && xd <= (double)(nx - 1) && yd >= 0.0 && yd <= (double)(ny - 1).  An unusable position gives undef for
+ *      every field and level at p.  -0.0 is inside; infinities are outside.
+ *   2. Cell.  i0 = (int)xd, j0 = (int)yd (truncation); a = xd - i0, b = yd - j0 (double, exact).  Column i0 + 1 is read
+ *      only when a != 0, row j0 + 1 only when b != 0: x == nx - 1 is legal and reads nothing outside the grid, and so is
+ *      nx == 1 or ny == 1.
+ *   3. A value v of field f, level k is defined iff is_defined(fdefined_in[f * nlev + k] == ALL_DEFINED, v, undef): a
+ *      stored undef under ALL_DEFINED is a value.
+ *   4. MIFC_HINTERP_NEAREST = 0: i = (int)(xd + 0.5), j = (int)(yd + 0.5); the result is field[k][j][i] bit for bit if
+ *      that value is defined, else undef.
+ *   5. MIFC_HINTERP_BILINEAR = 1: the needed corners are (j0, i0) always, (j0, i0 + 1) iff a != 0, (j0 + 1, i0) iff
+ *      b != 0, (j0 + 1, i0 + 1) iff both.  If any needed corner is undefined the result is undef.  Otherwise, the corners
+ *      widened to double, r0 = a == 0 ? x00 : x00 + a * (x10 - x00); b == 0: the result is (float)r0 (a point on a node
+ *      returns the node bit for bit); otherwise r1 = a == 0 ? x01 : x01 + a * (x11 - x01) and the result is
+ *      (float)(r0 + b * (r1 - r0)).
+ *   6. MIFC_HINTERP_BICUBIC = 2 (Catmull-Rom) applies only when a != 0 || b != 0, 1 <= i0 <= nx - 3 and
+ *      1 <= j0 <= ny - 3, and all 16 values of the rows j0 - 1 .. j0 + 2 by the columns i0 - 1 .. i0 + 2 are defined;
+ *      if any of these fails, that (point, field, level) follows rule 5 unchanged.  Weights in double, t = a for the
+ *      columns and t = b for the rows: w-1 = ((-0.5 * t + 1.0) * t - 0.5) * t, w0 = ((1.5 * t - 2.5) * t) * t + 1.0,
+ *      w1 = ((-1.5 * t + 2.0) * t + 0.5) * t, w2 = ((0.5 * t - 0.5) * t) * t.  Row sums
+ *      s_m = ((w-1 * x_m,-1 + w0 * x_m,0) + w1 * x_m,1) + w2 * x_m,2 for the four rows; the result is
+ *      (float)(((wy-1 * s_-1 + wy0 * s_0) + wy1 * s_1) + wy2 * s_2).
+ *   7. Flags.  fdefined_out[f * nlev + k] = checkDefined(points that rules 1, 4, 5 left undef, npos).  A computed result
+ *      is never counted, whatever its value.
+ * Every operation is an IEEE float or double operation rounded on its own (no contraction): results are bit for bit this
+ * definition (restated in numpy in tests/hinterp_restate.py).
+ * Arguments: `fields`, `fdefined_in`, nfields (1..8), undef and memkind as for mifc_vderiv_fields: `fields` a HOST array
+ * of nfields pointers to [nlev][ny][nx] batches, `fdefined_in` a HOST int[nfields * nlev] or NULL (all SOME_DEFINED).
+ * `xpos`, `ypos` are float[npos] and live where memkind says, like the fields; `fres` is a HOST array of nfields
+ * pointers, each to [nlev][npos] in the same memory kind; `fdefined_out` a HOST int[nfields * nlev].  Any alignment of
+ * any pointer is accepted.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 1; nfields outside
+ * 1..8; npos < 1; nx < 1 or ny < 1; nx * ny > 2^31 - 1; an unknown method; a null pointer that is required; an output
+ * that overlaps a field, xpos, ypos or another output by byte range; a bad memkind; a call made while a mifc_graph
+ * capture is open.
+ * Device memory is used where it is: no copies, one synchronisation at the end.  Host memory works at any size: levels
+ * are independent, so the positions are uploaded once and the call stages whole levels of every field at a time,
+ * MIFC_HINTERP_CHUNK_MIB of device memory (default 256) but never less than one level.
+ * mifc_last_hinterp_form: the launch shape of the calling thread's last mifc_hinterp_levels call, a diagnostic for
+ * tests: "method=<name> nf=<fields per launch> tested=0|1 blocks=<grid.x> level_chunks=<grid.y> chunk=<levels per
+ * chunk> launches=<n>"; "" before the first call. */
+enum { MIFC_HINTERP_NEAREST = 0, MIFC_HINTERP_BILINEAR = 1, MIFC_HINTERP_BICUBIC = 2 };
+int mifc_hinterp_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        int npos, const float* xpos, const float* ypos, int method,
+                        float* const* fres, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_hinterp_form(void);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

@@ -34,6 +34,8 @@ _ENS_MAX_PROBABILITIES = 8
 VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max": 5, "coord_of_min": 6}
 # the methods of mifc_vderiv_* (MIFC_VDERIV_*)
 VDERIV_METHODS = {"centred": 0, "weighted": 1}
+# the methods of mifc_hinterp_levels (MIFC_HINTERP_*)
+HINTERP_METHODS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 
 
 def ensemble_products(products):
@@ -880,6 +882,50 @@ class Context:
         """EXTENSION (include/mifc.h, mifc_vderiv_levels): as vderiv_hlevels, the coordinate one constant per level
         (pressure levels, the targets of an earlier vinterp call): `levels` holds nlev numbers."""
         return self._vderiv("mifc_vderiv_levels", fields, levels, [], method, magnitude, fdefined_in, undef, out)
+
+    # ------------------------------------------ level batches sampled at arbitrary points (EXTENSION)
+    def hinterp_levels(self, fields, xpos, ypos, method="bilinear", fdefined_in=None, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_hinterp_levels): level batches sampled at arbitrary positions -- a section line,
+        stations, the grid of another projection -- by "nearest", "bilinear" or "bicubic" (Catmull-Rom, bilinear next to
+        holes and in the outer ring of cells) interpolation, or a MIFC_HINTERP_* code.  fields, fdefined_in: as
+        vderiv_fields takes them.  xpos, ypos: numpy arrays (host memory) or CUDA tensors (device), like the fields, of any
+        one shape S, in grid-index units (x = 0 is column 0, x = nx - 1 the last column); a position outside the grid, NaN
+        or equal to undef gives undef.  Returns (out (nf, nlev) + S, flags int32 (nf, nlev)); with ONE (nlev, ny, nx)
+        batch for `fields` the leading axis is dropped from both.  A 2-D S is a regrid; a 1-D S gives (nlev, npos), which
+        reshaped to (nlev, 1, npos) is a level batch for vinterp_*, vlayer_* and vderiv_*.  Vector components are not
+        rotated.  A refused call raises RuntimeError."""
+        code = HINTERP_METHODS.get(method, -1) if isinstance(method, str) else int(method)
+        one, batches, fa, shape = _level_batches(fields)
+        nlev, ny, nx = shape
+        nf = len(fa)
+        xa, ya = _Arg(xpos), _Arg(ypos)
+        where = tuple(xa.shape)
+        if tuple(ya.shape) != where:
+            raise ValueError("xpos and ypos must have the same shape")
+        npos = int(np.prod(where, dtype=np.int64))
+        out_shape = ((nlev,) if one else (nf, nlev)) + where
+        if out is None:
+            out = _empty_like(batches[0], out_shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != out_shape:
+            raise ValueError("out must have shape %s" % (out_shape,))
+        mk = _memkind(fa + [xa, ya, oa], self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * nf)(*[oa.addr + f * nlev * npos * 4 for f in range(nf)])
+        flags = _level_flags(fdefined_in, nf, nlev)
+        fd = np.zeros((nf, nlev), np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf, npos, xa.addr, ya.addr, code, ctypes.addressof(outs), fd, float(undef), mk]
+        if not self._call("mifc_hinterp_levels", args):
+            raise RuntimeError("mifc_hinterp_levels: " + self.last_error())
+        res = out if _is_torch(out) else oa.keep
+        return (res, fd[0]) if one else (res, fd)
+
+    def last_hinterp_form(self):
+        """The launch shape of this thread's last hinterp_levels call as a dict (mifc_last_hinterp_form; a diagnostic for
+        tests): method as a string, the other keys as ints."""
+        form = dict(word.split("=", 1) for word in self._lib.mifc_last_hinterp_form().decode().split())
+        return {k: (v if k == "method" else int(v)) for k, v in form.items()}
 
     def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
         """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability

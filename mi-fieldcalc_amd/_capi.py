@@ -133,6 +133,9 @@ SIGNATURES = {
     "mifc_vderiv_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
     "mifc_vderiv_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "p", "pi", "p", "pi", "f", "i"]),
     "mifc_vderiv_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
+    # EXTENSION: level batches sampled at arbitrary points (fields, fres: host tables of pointers; xpos, ypos: where the fields are)
+    "mifc_hinterp_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
+    "mifc_last_hinterp_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

@@ -426,6 +426,52 @@ struct VderivParams
 };
 hipError_t launch_vderiv(const VderivParams& prm, hipStream_t stream);
 
+// ------------------------------------ level batches sampled at arbitrary points (mifc_hinterp.hip), EXTENSION
+// One launch samples `nlev` levels of up to hinterp_pass_fields(method) fields at `npos` points: a gather.  A lane owns
+// one point, a workgroup 256 consecutive points and the levels [blockIdx.y * chunk, + chunk) of the launch; level k of
+// field f lies at fields[f] + k * in_stride ([ny][nx]) and is written to out[f] + k * out_stride ([npos]).  The launch's
+// level 0 is level lev0 of the call: lev_bits[lev0 + k] bit f0 + f = field f of the launch is flagged ALL_DEFINED there
+// (read only by the tested instances), the counters are n_undefined[(f0 + f) * call_nlev + lev0 + k], zeroed by the
+// caller.  Points whose position is unusable (rule 1 of include/mifc.h) are written as undef at every level and counted
+// ONCE, into *n_unusable, by the workgroups of level chunk 0 of a launch with count_unusable set; the caller adds that
+// number to every counter.  xpos, ypos: [npos].  Every access is a single dword: any alignment of any pointer.
+const int HINTERP_MAX_FIELDS = 8, HINTERP_PASS = 4, HINTERP_PASS_BICUBIC = 2, HINTERP_UNROLL = 2;
+const int HINTERP_NEAREST = 0, HINTERP_BILINEAR = 1, HINTERP_BICUBIC = 2;
+constexpr int hinterp_pass_fields(int method)
+{
+  return method == HINTERP_BICUBIC ? HINTERP_PASS_BICUBIC : HINTERP_PASS;
+}
+struct HinterpParams
+{
+  int method;  // HINTERP_*
+  int nfields; // of this launch, 1 .. hinterp_pass_fields(method)
+  int f0;      // the call's field of the launch's field 0 (level bits, counters)
+  int nx, ny;
+  int npos;
+  int nlev;      // levels of this launch
+  int lev0;      // the call's level of the launch's level 0
+  int call_nlev; // levels of the call: the row length of the counters
+  int chunk;     // levels per workgroup: grid.y = ceil(nlev / chunk) (set by launch_hinterp from hinterp_plan)
+  int tested;    // 0: every level of every field of the call is ALL_DEFINED, no value is tested
+  int count_unusable;
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[HINTERP_PASS];
+  float* out[HINTERP_PASS];
+  const float *xpos, *ypos;
+  const unsigned int* lev_bits;
+  u64 *n_undefined, *n_unusable;
+};
+// The launch shape, the one rule for it: ceil(npos / 256) workgroups per level chunk, and the levels cut into as many
+// chunks as it takes to give every CU eight workgroups where nlev allows -- but chunks of HINTERP_UNROLL levels at least,
+// so that the loads of two levels are in flight.  Large npos: one chunk.  (MIFC_HINTERP_LEVEL_CHUNK overrides the chunk.)
+struct HinterpPlan
+{
+  int blocks, chunk, level_chunks;
+};
+HinterpPlan hinterp_plan(int npos, int nlev);
+hipError_t launch_hinterp(const HinterpParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843

@@ -1,6 +1,7 @@
 // mifc_levelbatch.h -- the host driver of the entries that walk level batches column by column (mifc_capi_vinterp.hip,
-// mifc_capi_vlayer.hip, mifc_capi_vderiv.hip): the head of such a call and the refusals that read only
-// it, the overlap rule, the device table of the per-level scalars, and where the planes of the call are on the device --
+// mifc_capi_vlayer.hip, mifc_capi_vderiv.hip; the head, the refusals and the level table also serve
+// mifc_capi_hinterp.hip, which samples the levels instead of walking them): the head of such a call and the refusals
+// that read only it, the overlap rule, the device table of the per-level scalars, and where the planes of the call are on the device --
 // the caller's own for device memory, a band of rows at a time for host memory (columns are independent, so a band of
 // every level is a complete problem).  Implemented in mifc_levelbatch.hip.
 #ifndef MIFC_LEVELBATCH_H
@@ -81,6 +82,7 @@ public:
   const void* dev_tail() const { return dev_ + o_tail_; }
   int read_counts(mifc_ctx* c); // behind the last launch, in front of Staging::finish()
   int classify(size_t counter, size_t cells) const { return mifc_classify(counts_[counter], (u64)cells); }
+  u64 count(size_t counter) const { return counts_[counter]; } // (an entry that adds a common counter to the others classifies itself)
 
 private:
   std::vector<unsigned char> host_;
