@@ -531,8 +531,8 @@ int mifc_vderiv_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
  * and npos positions go in, fres[f] is [nlev][npos] -- itself a level batch of shape (nlev, 1, npos), which
  * mifc_vinterp_*, mifc_vlayer_* and mifc_vderiv_* take unchanged: a vertical cross-section on pressure surfaces is this
  * call on the fields and on the pressure batch (or ps), then mifc_vinterp_*.  Positions are in grid-index units: x = 0 is
- * column 0, x = nx - 1 the last column.  Rotating vector components between projections is OUT OF SCOPE: the caller
- * rotates u, v with field algebra (mifc_fieldOPERfield).  Per point p, field f and level k:
+ * column 0, x = nx - 1 the last column.  Vector components are not rotated by this call: mifc_hinterp_vector_levels
+ * below samples pairs and rotates them in the same pass.  Per point p, field f and level k:
  *   1. Position.  x = xpos[p], y = ypos[p].  The position is unusable if !is_defined(false, x, undef) or
  *      !is_defined(false, y, undef) (NaN, or equal to undef), and, with xd = (double)x, yd = (double)y, unless
  *      xd >= 0.0 && xd <= (double)(nx - 1) && yd >= 0.0 && yd <= (double)(ny - 1).  An unusable position gives undef for
@@ -580,6 +580,60 @@ int mifc_hinterp_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* co
                         int npos, const float* xpos, const float* ypos, int method,
                         float* const* fres, int* fdefined_out, float undef, int memkind);
 const char* mifc_last_hinterp_form(void);
+
+/* ---- EXTENSION: vector pairs of level batches rotated, on the grid and while sampling -------------------------
+ * Not a miutil::fieldcalc function: a vector on a grid whose axes are not east and north (a rotated or polar-stereographic
+ * model; wind regridded to another projection; along- and across-section wind) has to be rotated point by point.  With
+ * field algebra that is six mifc_fieldOPERfield calls per pair and level, 72 B per cell where 16 B do, every product
+ * rounded to float.  Two entries share one rule.
+ *
+ * Rule R, the rotation.  It applies per cell or point, per pair q and per level k.
+ *   R1. The coefficients are c = cosa[p] and s = sina[p], one value per cell or point, shared by all levels and pairs.
+ *       They are defined iff is_defined(fdef_rot == ALL_DEFINED, c, s, undef).  The library does not normalise them.  The
+ *       sign convention is the caller's; the usual one gives u' = c*u - s*v, v' = s*u + c*v.
+ *   R2. A pair result is a hole, and both outputs are undef, if any of these is undefined: the coefficients; u; v.  Each
+ *       component is tested by its own input flag: a stored undef under ALL_DEFINED is a value.
+ *   R3. Otherwise all four values are widened to double, and u' = (float)(c*u - s*v), v' = (float)(s*u + c*v).  Every
+ *       operation is rounded on its own, with no contraction.  The two products are exact in double (24 x 24 bits).  Each
+ *       result therefore carries one double rounding and one float rounding.  With (c, s) = (1, 0) a pair comes back bit
+ *       for bit, except the sign of a zero: u = -0.0, v = -3 gives +0.0.
+ *   R4. Flags: fdefined_out[(2q) * nlev + k] = fdefined_out[(2q + 1) * nlev + k] = checkDefined(holes of pair q at level
+ *       k, number of cells or points).
+ * (Restated in numpy in tests/vrotate_restate.py.)
+ *
+ * mifc_vrotate_levels, on the grid.  `fields` is a HOST array of 2 * npairs pointers (u0, v0, u1, v1, ...) to
+ * [nlev][ny][nx] batches, npairs 1..4; `fdefined_in` a HOST int[2 * npairs * nlev] in that order or NULL (all
+ * SOME_DEFINED); cosa, sina are [ny][nx] and live where memkind says, like the fields; `fres` is laid out like `fields`,
+ * `fdefined_out` like `fdefined_in`.  nlev == 1 is legal.  In-place is not offered.  Refused calls return 0, write
+ * nothing and give the reason in mifc_last_error(): nlev < 1; npairs outside 1..4; nx < 1 or ny < 1; nx * ny > 2^31 - 1;
+ * a null pointer; an output that overlaps a field, cosa, sina or another output by byte range; a bad memkind; a call made
+ * while a mifc_graph capture is open.  Device memory is used where it is (four cells per lane through 16-byte accesses
+ * where every pointer and the level size allow, else one); host memory works at any size: cells are independent, so the
+ * call stages a band of rows of every level and of the coefficients at a time (MIFC_VDERIV_CHUNK_MIB of device memory,
+ * default 256, the budget of the other vector product).  mifc_last_vrotate_form: the launch shape of the calling thread's
+ * last mifc_vrotate_levels call, a diagnostic for tests: "v=4|1 np=<pairs per launch> tested=0|1 blocks=<grid.x>
+ * level_chunks=<grid.y> chunk=<levels per chunk> launches=<n>"; "" before the first call.
+ *
+ * mifc_hinterp_vector_levels, while sampling: mifc_hinterp_levels with npairs (1..4) in the place of nfields, `fields`,
+ * `fres` and the flags laid out as above, and cosa, sina (float[npos], where memkind says) and fdef_rot behind ypos.  Each
+ * component is sampled exactly by rules 1-7 of mifc_hinterp_levels, including its own bicubic-or-bilinear decision, and
+ * rounded to float; the two floats are then rotated by rule R with the point's coefficients.  By definition the call
+ * equals two calls bit for bit, flags included: mifc_hinterp_levels, then mifc_vrotate_levels on the (nlev, 1, npos)
+ * batches with the flags of the first call and the coefficients as a (1, npos) plane.  A component is undefined (R2) where
+ * rules 1, 4 and 5 left a hole.  The one call carries these holes, the second of two calls can only recognise them by
+ * their value: the two differ where a component flagged ALL_DEFINED stores undef or NaN all the same -- the sampling hands
+ * such a value on as the value it is (rule 3), this call rotates it, two calls take it for a hole.  A point whose
+ * coefficients are undefined is treated like an unusable position: undef for every pair and level, counted once.  The refusals are those
+ * of mifc_hinterp_levels ("npairs <n> outside 1..4"; cosa and sina may not be null nor overlap an output); host memory is
+ * staged in whole levels (MIFC_HINTERP_CHUNK_MIB).  The call reports through mifc_last_hinterp_form, nf = the components
+ * per launch (2 or 4). */
+int mifc_vrotate_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int npairs,
+                        const float* cosa, const float* sina, int fdef_rot, float* const* fres, int* fdefined_out, float undef,
+                        int memkind);
+const char* mifc_last_vrotate_form(void);
+int mifc_hinterp_vector_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int npairs,
+                               int npos, const float* xpos, const float* ypos, const float* cosa, const float* sina, int fdef_rot,
+                               int method, float* const* fres, int* fdefined_out, float undef, int memkind);
 
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the

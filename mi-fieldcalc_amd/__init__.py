@@ -893,7 +893,7 @@ class Context:
         or equal to undef gives undef.  Returns (out (nf, nlev) + S, flags int32 (nf, nlev)); with ONE (nlev, ny, nx)
         batch for `fields` the leading axis is dropped from both.  A 2-D S is a regrid; a 1-D S gives (nlev, npos), which
         reshaped to (nlev, 1, npos) is a level batch for vinterp_*, vlayer_* and vderiv_*.  Vector components are not
-        rotated.  A refused call raises RuntimeError."""
+        rotated: hinterp_vector_levels does that in the same pass.  A refused call raises RuntimeError."""
         code = HINTERP_METHODS.get(method, -1) if isinstance(method, str) else int(method)
         one, batches, fa, shape = _level_batches(fields)
         nlev, ny, nx = shape
@@ -926,6 +926,113 @@ class Context:
         tests): method as a string, the other keys as ints."""
         form = dict(word.split("=", 1) for word in self._lib.mifc_last_hinterp_form().decode().split())
         return {k: (v if k == "method" else int(v)) for k, v in form.items()}
+
+    # ------------------------------------------ vector pairs rotated, on the grid and while sampling (EXTENSION)
+    @staticmethod
+    def _pairs(pairs):
+        """The components u0, v0, u1, v1 ... of `pairs` -- one pair (2, nlev, ny, nx), stacked pairs (npairs, 2, nlev, ny, nx),
+        a sequence of (u, v) or the flat sequence u0, v0, u1, v1 ... of (nlev, ny, nx) batches -- as _level_batches takes
+        them: (was it one pair, the batches, their _Arg, the shape of a batch)."""
+        stacked = isinstance(pairs, np.ndarray) or _is_torch(pairs)
+        if stacked and len(pairs.shape) not in (4, 5):
+            raise ValueError("pairs must be (2, nlev, ny, nx), (npairs, 2, nlev, ny, nx) or a sequence of (u, v)")
+        items = [pairs[j] for j in range(pairs.shape[0])] if stacked else list(pairs)
+        if items and all(hasattr(i, "shape") and len(i.shape) == 3 for i in items):
+            comps, one = items, len(items) == 2  # u, v (, u1, v1 ...)
+        else:
+            comps, one = [], False
+            for pair in items:
+                if len(pair) != 2:
+                    raise ValueError("a pair is (u, v)")
+                comps += [pair[0], pair[1]]
+        if len(comps) < 2 or len(comps) % 2:
+            raise ValueError("pairs must hold u and v of every pair")
+        _, batches, fa, shape = _level_batches(comps)
+        return one, batches, fa, shape
+
+    @staticmethod
+    def _pair_flags(fdefined_in, npairs, nlev):
+        """fdefined_in of a pair call -- (2,), (2, nlev), (npairs, 2) or (npairs, 2, nlev) -- as the (2 * npairs, nlev) table."""
+        if fdefined_in is None:
+            return None
+        f = np.asarray(fdefined_in, dtype=np.int32)
+        if f.size == 2 * npairs:
+            f = np.repeat(f.reshape(2 * npairs, 1), nlev, axis=1)
+        return np.ascontiguousarray(f.reshape(2 * npairs, nlev), dtype=np.int32)
+
+    def vrotate_levels(self, pairs, cosa, sina, fdefined_in=None, fdef_rot=SOME_DEFINED, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_vrotate_levels, rule R): vector pairs of level batches rotated cell by cell,
+        u' = c u - s v, v' = s u + c v in double, rounded to float once.  pairs: one pair (2, nlev, ny, nx), up to four
+        stacked (npairs, 2, nlev, ny, nx), or a sequence of (u, v) batches; numpy arrays (host memory) or CUDA tensors.
+        cosa, sina: (ny, nx), like the fields; the library does not normalise them; fdef_rot: their flag.  fdefined_in: one
+        flag per component or per component and level, None: SOME_DEFINED.  Returns (out, flags): out shaped like the
+        stacked pairs, flags int32 (npairs, 2, nlev) -- the two components of a pair carry the same flag; with ONE pair the
+        leading axis is dropped from both.  A refused call raises RuntimeError."""
+        one, batches, fa, shape = self._pairs(pairs)
+        nlev, ny, nx = shape
+        nf = len(fa)
+        ca, sa = _Arg(cosa), _Arg(sina)
+        if tuple(ca.shape) != (ny, nx) or tuple(sa.shape) != (ny, nx):
+            raise ValueError("cosa and sina must have the shape %s" % ((ny, nx),))
+        out_shape = ((2,) if one else (nf // 2, 2)) + shape
+        if out is None:
+            out = _empty_like(batches[0], out_shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != out_shape:
+            raise ValueError("out must have shape %s" % (out_shape,))
+        mk = _memkind(fa + [ca, sa, oa], self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * nf)(*[oa.addr + f * nlev * ny * nx * 4 for f in range(nf)])
+        flags = self._pair_flags(fdefined_in, nf // 2, nlev)
+        fd = np.zeros((nf // 2, 2, nlev), np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf // 2, ca.addr, sa.addr, int(fdef_rot), ctypes.addressof(outs), fd, float(undef), mk]
+        if not self._call("mifc_vrotate_levels", args):
+            raise RuntimeError("mifc_vrotate_levels: " + self.last_error())
+        res = out if _is_torch(out) else oa.keep
+        return (res, fd[0]) if one else (res, fd)
+
+    def last_vrotate_form(self):
+        """The launch shape of this thread's last vrotate_levels call as a dict of ints (mifc_last_vrotate_form; a diagnostic
+        for tests)."""
+        return {k: int(v) for k, v in (word.split("=", 1) for word in self._lib.mifc_last_vrotate_form().decode().split())}
+
+    def hinterp_vector_levels(self, pairs, xpos, ypos, cosa, sina, method="bilinear", fdefined_in=None, fdef_rot=SOME_DEFINED, undef=UNDEF,
+                              out=None):
+        """EXTENSION (include/mifc.h, mifc_hinterp_vector_levels): hinterp_levels of vector pairs and their rotation by rule R
+        in one pass -- wind regridded to another projection, along- and across-section wind.  pairs, fdefined_in, fdef_rot:
+        as vrotate_levels takes them; xpos, ypos, method: as hinterp_levels takes them; cosa, sina: one value per position,
+        shaped like xpos.  A position with undefined coefficients gives undef like an unusable one.  Returns (out
+        (npairs, 2, nlev) + S, flags int32 (npairs, 2, nlev)), bit for bit hinterp_levels followed by vrotate_levels; with
+        ONE pair the leading axis is dropped from both.  The launch shape is in last_hinterp_form().  A refused call raises
+        RuntimeError."""
+        code = HINTERP_METHODS.get(method, -1) if isinstance(method, str) else int(method)
+        one, batches, fa, shape = self._pairs(pairs)
+        nlev, ny, nx = shape
+        nf = len(fa)
+        xa, ya, ca, sa = _Arg(xpos), _Arg(ypos), _Arg(cosa), _Arg(sina)
+        where = tuple(xa.shape)
+        if not _same_shape([ya, ca, sa], where):
+            raise ValueError("xpos, ypos, cosa and sina must have the same shape")
+        npos = int(np.prod(where, dtype=np.int64))
+        out_shape = ((2, nlev) if one else (nf // 2, 2, nlev)) + where
+        if out is None:
+            out = _empty_like(batches[0], out_shape)
+        oa = _Arg(out, output=True)
+        if tuple(oa.shape) != out_shape:
+            raise ValueError("out must have shape %s" % (out_shape,))
+        mk = _memkind(fa + [xa, ya, ca, sa, oa], self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        outs = (ctypes.c_void_p * nf)(*[oa.addr + f * nlev * npos * 4 for f in range(nf)])
+        flags = self._pair_flags(fdefined_in, nf // 2, nlev)
+        fd = np.zeros((nf // 2, 2, nlev), np.int32)
+        args = [nx, ny, nlev, ctypes.addressof(table), flags, nf // 2, npos, xa.addr, ya.addr, ca.addr, sa.addr, int(fdef_rot), code,
+                ctypes.addressof(outs), fd, float(undef), mk]
+        if not self._call("mifc_hinterp_vector_levels", args):
+            raise RuntimeError("mifc_hinterp_vector_levels: " + self.last_error())
+        res = out if _is_torch(out) else oa.keep
+        return (res, fd[0]) if one else (res, fd)
 
     def ensembleStatistics(self, fields, products, fdefined_in=None, undef=UNDEF, out=None):
         """mifc_ensemble_levels (include/mifc.h): several of sumFields, meanValue, stddevValue, extremeValue and probability

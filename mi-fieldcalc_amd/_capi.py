@@ -136,6 +136,10 @@ SIGNATURES = {
     # EXTENSION: level batches sampled at arbitrary points (fields, fres: host tables of pointers; xpos, ypos: where the fields are)
     "mifc_hinterp_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_last_hinterp_form": ("s", []),
+    # EXTENSION: vector pairs rotated on the grid and while sampling (fields, fres: host tables of 2 * npairs pointers)
+    "mifc_vrotate_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "p", "i", "p", "pi", "f", "i"]),
+    "mifc_last_vrotate_form": ("s", []),
+    "mifc_hinterp_vector_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "p", "p", "i", "i", "p", "pi", "f", "i"]),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

@@ -1,4 +1,6 @@
-// mifc_capi_hinterp.hip -- C ABI of mifc_hinterp_levels (include/mifc.h; EXTENSION, no reference function): its refusals
+// mifc_capi_hinterp.hip -- C ABI of mifc_hinterp_levels and mifc_hinterp_vector_levels (include/mifc.h; EXTENSION, no
+// reference function), one driver for both -- the vector form samples pairs and rotates them by rule R in the same
+// launch (the ROTATE form of the kernel; the coefficients go up once, with the positions): its refusals
 // (the head of the call, the overlap rule and the level table are the ones of mifc_levelbatch.h), the passes over the
 // fields -- four per launch of the kernel of mifc_hinterp.hip, two with the bicubic method -- and, for host memory, the
 // chunks of levels.  Levels are independent and a point may need any cell of a level, so host batches are staged whole
@@ -32,21 +34,27 @@ size_t levels_per_chunk(size_t budget, size_t nfields, size_t cells, size_t npos
   return std::max<size_t>(1, std::min<size_t>(nlev, budget / per_level));
 }
 
-} // namespace
+// the vector form: the fields are pairs u0, v0, u1, v1 ..., rotated with cosa[p], sina[p] (null: the plain form)
+struct Rotation
+{
+  int npairs;
+  const float *cosa, *sina;
+  int fdef_rot;
+};
 
-extern "C" {
-
-int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields, int npos,
-                        const float* xpos, const float* ypos, int method, float* const* fres, int* fdefined_out, float undef, int memkind)
+int run(mifc_ctx* c, const char* name, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields, int npos,
+        const float* xpos, const float* ypos, const Rotation* rot, int method, float* const* fres, int* fdefined_out, float undef, int memkind)
 {
   CTX_OR_FAIL(c);
   // (the head of a level-batch call without a coordinate: what the shared checks and the level table read)
-  const LevelBatchCall a = {"mifc_hinterp_levels", COORD_LEVELS, nx, ny, nlev, fields, fdefined_in, nfields, nullptr, MIFC_SOME_DEFINED, nullptr,
+  const LevelBatchCall a = {name, COORD_LEVELS, nx, ny, nlev, fields, fdefined_in, nfields, nullptr, MIFC_SOME_DEFINED, nullptr,
                             nullptr, nullptr, undef, memkind};
   if (c->capturing)
     return refuse(c, a, "not available while a mifc_graph capture is open");
   if (nlev < 1)
     return refuse(c, a, "nlev < 1");
+  if (rot && nfields == 0)
+    return refuse(c, a, "npairs " + std::to_string(rot->npairs) + " outside 1.." + std::to_string(mifc::HINTERP_MAX_FIELDS / 2));
   if (nfields < 1 || nfields > mifc::HINTERP_MAX_FIELDS)
     return refuse(c, a, "nfields " + std::to_string(nfields) + " outside 1.." + std::to_string(mifc::HINTERP_MAX_FIELDS));
   if (npos < 1)
@@ -57,6 +65,8 @@ int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
     return 0;
   if (method != MIFC_HINTERP_NEAREST && method != MIFC_HINTERP_BILINEAR && method != MIFC_HINTERP_BICUBIC)
     return refuse(c, a, "unknown method " + std::to_string(method));
+  if (rot && (!fields || !xpos || !ypos || !rot->cosa || !rot->sina || !fres || !fdefined_out))
+    return refuse(c, a, "a null pointer (fields, xpos, ypos, cosa, sina, fres or fdefined_out)");
   if (!fields || !xpos || !ypos || !fres || !fdefined_out)
     return refuse(c, a, "a null pointer (fields, xpos, ypos, fres or fdefined_out)");
   if (!check_field_pointers(c, a, fres))
@@ -64,19 +74,23 @@ int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
   const int nf = nfields;
   const size_t cells = a.cells(), points = (size_t)npos, levels = (size_t)nlev;
   if (!check_overlaps(c, a, {{fres, nf, levels * points * sizeof(float), "fres"}},
-                      {{xpos, points * sizeof(float), "xpos"}, {ypos, points * sizeof(float), "ypos"}}))
+                      {{xpos, points * sizeof(float), "xpos"},
+                       {ypos, points * sizeof(float), "ypos"},
+                       {rot ? rot->cosa : nullptr, points * sizeof(float), "cosa"},
+                       {rot ? rot->sina : nullptr, points * sizeof(float), "sina"}}))
     return 0;
 
-  const size_t n_counts = (size_t)nf * levels; // then the one counter of the unusable positions
+  // one counter per field and level -- per PAIR and level in the vector form --, then the one of the unusable positions
+  const size_t n_results = rot ? (size_t)(nf / 2) : (size_t)nf, n_counts = n_results * levels;
   LevelTable tab;
   Staging st(c, memkind);
   if (!tab.build(c, a, n_counts + 1) || !tab.upload(c, st))
     return 0;
   bool tested = false;
-  for (size_t j = 0; j < n_counts; ++j)
+  for (size_t j = 0; j < (size_t)nf * levels; ++j)
     tested |= !fdefined_in || fdefined_in[j] != MIFC_ALL_DEFINED;
 
-  mifc::HinterpParams P;
+  mifc::HinterpRotateParams P; // (the plain form launches its HinterpParams part)
   std::memset(&P, 0, sizeof P);
   P.method = method;
   P.nx = nx;
@@ -92,6 +106,11 @@ int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
   P.n_unusable = tab.n_undefined() + n_counts;
   P.xpos = st.in(xpos, points);
   P.ypos = st.in(ypos, points);
+  if (rot) {
+    P.cosa = st.in(rot->cosa, points);
+    P.sina = st.in(rot->sina, points);
+    P.rot_all = rot->fdef_rot == MIFC_ALL_DEFINED ? 1 : 0;
+  }
   if (!st.ok())
     return 0;
 
@@ -137,7 +156,10 @@ int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
         P.fields[f] = in[f0 + f];
         P.out[f] = out[f0 + f];
       }
-      MIFC_LAUNCH(c, mifc::launch_hinterp(P, c->stream));
+      if (rot)
+        MIFC_LAUNCH(c, mifc::launch_hinterp_rotate(P, c->stream));
+      else
+        MIFC_LAUNCH(c, mifc::launch_hinterp(P, c->stream));
       form.launches += 1;
     }
     form.blocks = plan.blocks;
@@ -151,9 +173,36 @@ int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
     return 0;
   t_form = form;
   const u64 unusable = tab.count(n_counts);
-  for (size_t j = 0; j < n_counts; ++j)
-    fdefined_out[j] = mifc_classify(tab.count(j) + unusable, (u64)points);
+  for (size_t j = 0; j < n_counts; ++j) {
+    const int flag = mifc_classify(tab.count(j) + unusable, (u64)points);
+    if (rot) { // R4: both components of a pair carry the pair's flag
+      const size_t q = j / levels, k = j % levels;
+      fdefined_out[(2 * q) * levels + k] = fdefined_out[(2 * q + 1) * levels + k] = flag;
+    } else {
+      fdefined_out[j] = flag;
+    }
+  }
   return 1;
+}
+
+} // namespace
+
+extern "C" {
+
+int mifc_hinterp_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields, int npos,
+                        const float* xpos, const float* ypos, int method, float* const* fres, int* fdefined_out, float undef, int memkind)
+{
+  return run(c, "mifc_hinterp_levels", nx, ny, nlev, fields, fdefined_in, nfields, npos, xpos, ypos, nullptr, method, fres, fdefined_out, undef, memkind);
+}
+
+int mifc_hinterp_vector_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int npairs, int npos,
+                               const float* xpos, const float* ypos, const float* cosa, const float* sina, int fdef_rot, int method,
+                               float* const* fres, int* fdefined_out, float undef, int memkind)
+{
+  const Rotation rot = {npairs, cosa, sina, fdef_rot};
+  const int nfields = npairs >= 1 && npairs <= mifc::HINTERP_MAX_FIELDS / 2 ? 2 * npairs : 0; // (0: refused by name)
+  return run(c, "mifc_hinterp_vector_levels", nx, ny, nlev, fields, fdefined_in, nfields, npos, xpos, ypos, &rot, method, fres, fdefined_out, undef,
+             memkind);
 }
 
 const char* mifc_last_hinterp_form(void)

@@ -36,9 +36,11 @@ __device__ __forceinline__ void cubic_weights(double t, double (&w)[4])
   w[3] = ((0.5 * t - 0.5) * t) * t;
 }
 
-template <int METHOD, int NF, bool TESTED>
-__global__ __launch_bounds__(256) void hinterp_kernel(const HinterpParams P)
+// ROTATE: the fields of the launch are pairs; both components are sampled, then rotated by rule R with the point's coefficients
+template <int METHOD, int NF, bool TESTED, bool ROTATE = false>
+__global__ __launch_bounds__(256) void hinterp_kernel(const std::conditional_t<ROTATE, HinterpRotateParams, HinterpParams> P)
 {
+  static_assert(!ROTATE || NF % 2 == 0, "a pair stays in one launch");
   // values per (field, level): the node | the four corners | the 4 x 4 block, rows j0 - 1 .. j0 + 2 by columns i0 - 1 .. i0 + 2
   constexpr int NV = METHOD == HINTERP_NEAREST ? 1 : (METHOD == HINTERP_BILINEAR ? 4 : 16);
   // where the corners (j0, i0), (j0, i0 + 1), (j0 + 1, i0), (j0 + 1, i0 + 1) are among them
@@ -52,7 +54,14 @@ __global__ __launch_bounds__(256) void hinterp_kernel(const HinterpParams P)
   // rule 1, once per point
   const float x = P.xpos[mine ? p : 0u], y = P.ypos[mine ? p : 0u];
   const double xd = (double)x, yd = (double)y;
-  const bool usable = all_def(undef, x, y) && xd >= 0.0 && xd <= (double)(nx - 1) && yd >= 0.0 && yd <= (double)(ny - 1);
+  bool usable = all_def(undef, x, y) && xd >= 0.0 && xd <= (double)(nx - 1) && yd >= 0.0 && yd <= (double)(ny - 1);
+  double rc = 0.0, rs = 0.0; // rule R1, once per point, next to the position: undefined coefficients make the position unusable
+  if constexpr (ROTATE) {
+    const float cf = P.cosa[mine ? p : 0u], sf = P.sina[mine ? p : 0u];
+    usable &= P.rot_all != 0 || all_def(undef, cf, sf);
+    rc = (double)cf;
+    rs = (double)sf;
+  }
   const bool sampled = mine && usable; // the lane's results are computed values or counted holes
   const double xs = sampled ? xd : 0.0, ys = sampled ? yd : 0.0; // (every other lane reads cell 0 and throws it away)
   if (P.count_unusable != 0 && blockIdx.y == 0) {
@@ -163,18 +172,41 @@ __global__ __launch_bounds__(256) void hinterp_kernel(const HinterpParams P)
       unsigned int bits = 0;
       if constexpr (TESTED)
         bits = lev_bits[kc] >> P.f0;
+      if constexpr (ROTATE) {
 #pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        bool bad;
-        float r = result(v[u][f], ((bits >> f) & 1u) != 0, bad);
-        r = usable ? r : undef;
-        if constexpr (TESTED) {
-          const u64 m = __builtin_amdgcn_ballot_w64(bad && sampled);
-          if (m != 0 && lane0)
-            atomicAdd(P.n_undefined + (long)(P.f0 + f) * P.call_nlev + kc, (u64)__popcll(m));
+        for (int f = 0; f < NF; f += 2) { // the pair (f, f + 1): each component by rules 3 to 6 and rounded to float, then rule R
+          bool bad_u, bad_v;
+          const float su = result(v[u][f], ((bits >> f) & 1u) != 0, bad_u), sv = result(v[u][f + 1], ((bits >> (f + 1)) & 1u) != 0, bad_v);
+          const bool bad = bad_u | bad_v;
+          const double ud = (double)su, vd = (double)sv;
+          const double cu = rc * ud, svv = rs * vd, suu = rs * ud, cv = rc * vd;
+          const double ra = cu - svv, rb = suu + cv;
+          const bool hole = bad | !usable;
+          const float r0 = hole ? undef : (float)ra, r1 = hole ? undef : (float)rb;
+          if constexpr (TESTED) {
+            const u64 m = __builtin_amdgcn_ballot_w64(bad && sampled);
+            if (m != 0 && lane0)
+              atomicAdd(P.n_undefined + (long)((P.f0 + f) / 2) * P.call_nlev + kc, (u64)__popcll(m));
+          }
+          if (mine) {
+            (P.out[f] + (long)(k + u) * P.out_stride)[p] = r0;
+            (P.out[f + 1] + (long)(k + u) * P.out_stride)[p] = r1;
+          }
         }
-        if (mine)
-          (P.out[f] + (long)(k + u) * P.out_stride)[p] = r;
+      } else {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+          bool bad;
+          float r = result(v[u][f], ((bits >> f) & 1u) != 0, bad);
+          r = usable ? r : undef;
+          if constexpr (TESTED) {
+            const u64 m = __builtin_amdgcn_ballot_w64(bad && sampled);
+            if (m != 0 && lane0)
+              atomicAdd(P.n_undefined + (long)(P.f0 + f) * P.call_nlev + kc, (u64)__popcll(m));
+          }
+          if (mine)
+            (P.out[f] + (long)(k + u) * P.out_stride)[p] = r;
+        }
       }
     }
   };
@@ -187,28 +219,32 @@ __global__ __launch_bounds__(256) void hinterp_kernel(const HinterpParams P)
     levels(std::integral_constant<int, 1>(), k);
 }
 
-template <int METHOD, int NF>
-hipError_t launch_tested(const HinterpParams& P, hipStream_t stream)
+template <int METHOD, int NF, class Params>
+hipError_t launch_tested(const Params& P, hipStream_t stream)
 {
+  constexpr bool ROTATE = std::is_same<Params, HinterpRotateParams>::value;
   const dim3 grid((unsigned int)(((long)P.npos + 255) / 256), (unsigned int)((P.nlev + P.chunk - 1) / P.chunk)), block(256);
   if (P.tested)
-    hipLaunchKernelGGL((hinterp_kernel<METHOD, NF, true>), grid, block, 0, stream, P);
+    hipLaunchKernelGGL((hinterp_kernel<METHOD, NF, true, ROTATE>), grid, block, 0, stream, P);
   else
-    hipLaunchKernelGGL((hinterp_kernel<METHOD, NF, false>), grid, block, 0, stream, P);
+    hipLaunchKernelGGL((hinterp_kernel<METHOD, NF, false, ROTATE>), grid, block, 0, stream, P);
   return hipGetLastError();
 }
 
-template <int METHOD>
-hipError_t launch_nf(const HinterpParams& P, hipStream_t stream)
+template <int METHOD, class Params>
+hipError_t launch_nf(const Params& P, hipStream_t stream)
 {
   static_assert(HINTERP_PASS == 4 && HINTERP_PASS_BICUBIC == 2, "one case per field count of a launch");
+  constexpr bool ROTATE = std::is_same<Params, HinterpRotateParams>::value; // (pairs: no instances with an odd field count)
   switch (P.nfields) {
   case 1:
-    return launch_tested<METHOD, 1>(P, stream);
+    if constexpr (!ROTATE)
+      return launch_tested<METHOD, 1>(P, stream);
+    return hipErrorInvalidValue;
   case 2:
     return launch_tested<METHOD, 2>(P, stream);
   case 3:
-    if constexpr (hinterp_pass_fields(METHOD) >= 3)
+    if constexpr (hinterp_pass_fields(METHOD) >= 3 && !ROTATE)
       return launch_tested<METHOD, 3>(P, stream);
     return hipErrorInvalidValue; // (the instances beyond a launch's capacity do not exist)
   case 4:
@@ -239,12 +275,15 @@ HinterpPlan hinterp_plan(int npos, int nlev)
   return {blocks, chunk, (nlev + chunk - 1) / chunk};
 }
 
-hipError_t launch_hinterp(const HinterpParams& prm, hipStream_t stream)
+namespace {
+
+template <class Params>
+hipError_t launch_checked(const Params& prm, hipStream_t stream)
 {
   if (prm.npos < 1 || prm.nlev < 1 || prm.nx < 1 || prm.ny < 1 || (long)prm.nx * (long)prm.ny > 0x7fffffffL || prm.f0 < 0 ||
       prm.f0 + prm.nfields > HINTERP_MAX_FIELDS || prm.lev0 < 0 || prm.lev0 + prm.nlev > prm.call_nlev)
     return hipErrorInvalidValue;
-  HinterpParams P = prm;
+  Params P = prm;
   P.chunk = hinterp_plan(P.npos, P.nlev).chunk;
   switch (P.method) {
   case HINTERP_NEAREST:
@@ -256,6 +295,20 @@ hipError_t launch_hinterp(const HinterpParams& prm, hipStream_t stream)
   default:
     return hipErrorInvalidValue;
   }
+}
+
+} // namespace
+
+hipError_t launch_hinterp(const HinterpParams& prm, hipStream_t stream)
+{
+  return launch_checked(prm, stream);
+}
+
+hipError_t launch_hinterp_rotate(const HinterpRotateParams& prm, hipStream_t stream)
+{
+  if ((prm.f0 & 1) != 0 || (prm.nfields & 1) != 0 || !prm.cosa || !prm.sina)
+    return hipErrorInvalidValue;
+  return launch_checked(prm, stream);
 }
 
 } // namespace mifc

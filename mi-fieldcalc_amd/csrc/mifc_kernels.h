@@ -471,6 +471,54 @@ struct HinterpPlan
 };
 HinterpPlan hinterp_plan(int npos, int nlev);
 hipError_t launch_hinterp(const HinterpParams& prm, hipStream_t stream);
+// The ROTATE form (mifc_hinterp_vector_levels): the fields of the launch are pairs (u0, v0, u1, v1: nfields 2 or 4, 2 with
+// the bicubic method, f0 even); every component is sampled as above and rounded to float, then the pair is rotated by rule R
+// of include/mifc.h with the point's coefficients cosa[p], sina[p] (rot_all: fdef_rot == ALL_DEFINED).  A point whose
+// coefficients are undefined counts as an unusable position.  A hole of either component is a hole of the pair: both
+// outputs are undef there, and it is counted once, into n_undefined[(f0 / 2 + q) * call_nlev + lev0 + k].
+struct HinterpRotateParams : HinterpParams
+{
+  const float *cosa, *sina;
+  int rot_all;
+};
+hipError_t launch_hinterp_rotate(const HinterpRotateParams& prm, hipStream_t stream);
+
+// ------------------------------------ vector pairs of level batches rotated on the grid (mifc_vrotate.hip), EXTENSION
+// One launch rotates `nlev` levels of `npairs` pairs (u_q = fields[2q], v_q = fields[2q + 1]) at `n` cells by rule R of
+// include/mifc.h: a streaming kernel.  A lane owns V consecutive cells (vec4: four through 16-byte accesses, as in
+// VinterpParams; else one), a workgroup 256 lanes and the levels [blockIdx.y * chunk, + chunk); it reads its coefficients
+// cosa, sina (n floats each) once.  Level k of a field lies at fields[f] + k * in_stride and is written to
+// out[f] + k * out_stride.  lev_bits[k] bit f = field f is flagged ALL_DEFINED at level k (read only by the tested
+// instances); rot_all: fdef_rot == ALL_DEFINED.  tested == 0: every flag of the call and fdef_rot are ALL_DEFINED.
+// Counters: n_undefined[q * nlev + k], zeroed by the caller.
+const int VROTATE_MAX_PAIRS = 4, VROTATE_UNROLL = 2, VROTATE_CHUNK = 4;
+struct VrotateParams
+{
+  int npairs; // 1 .. VROTATE_MAX_PAIRS
+  int n;      // cells of this launch
+  int nlev;
+  int chunk; // levels per workgroup: grid.y = ceil(nlev / chunk) (set by launch_vrotate from vrotate_plan)
+  int tested;
+  int rot_all;
+  int vec4;
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[2 * VROTATE_MAX_PAIRS];
+  float* out[2 * VROTATE_MAX_PAIRS];
+  const float *cosa, *sina;
+  const unsigned int* lev_bits;
+  u64* n_undefined;
+};
+// The launch shape, the one rule for it: ceil(cells / (V * 256)) workgroups per level chunk, V = 4 or 1, and the levels cut
+// into chunks of VROTATE_CHUNK, the last one shorter: the length measured fastest on small and on large fields alike
+// (the coefficients are read once per chunk, 8 B per cell against the chunk's 64 * npairs).
+// (MIFC_HINTERP_LEVEL_CHUNK overrides the chunk of this walk too.)
+struct VrotatePlan
+{
+  int blocks, chunk, level_chunks;
+};
+VrotatePlan vrotate_plan(int cells, int nlev, int vec4 = 1);
+hipError_t launch_vrotate(const VrotateParams& prm, hipStream_t stream);
 
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
