@@ -635,6 +635,75 @@ int mifc_hinterp_vector_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const fl
                                int npos, const float* xpos, const float* ypos, const float* cosa, const float* sina, int fdef_rot,
                                int method, float* const* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: horizontal statistics of level batches: area and row reductions --------------------------------
+ * Not a miutil::fieldcalc function: the minimum and maximum of a field (a colour scale), an area-weighted domain mean, a
+ * zonal mean, the bias or RMSE between two batches are numbers, and the reference's callers copy the whole batch to the
+ * host for each of them.  This call turns a device-resident batch into numbers; its row-wise mean is itself a level batch
+ * of shape (nlev, nrows, 1) that mifc_vinterp_fields takes, and the (nlev, 1, npos) output of mifc_hinterp_levels can be
+ * reduced in turn.  Results are reproducible bit for bit whatever the launch shape, the memory kind or the staging: the
+ * order of every addition is part of the definition.
+ * Inputs: fields[f], up to 8 batches [nlev][ny][nx], with flags fdefined_in[f * nlev + k] (NULL: SOME_DEFINED); optional
+ * minus[f], batches of the same shape with flags fdefined_minus (minus == NULL: none; it may not be given for only some
+ * fields); optional pivot, a HOST double[nfields * nlev] (NULL: 0.0); optional weight, a float [ny][nx] shared by all
+ * levels and fields, with one flag fdef_weight; optional box, a HOST int[4] = {i0, i1, j0, j1}, half-open (NULL: the whole
+ * level); mode MIFC_HSTATS_AREA (one result per field and level, nrows = 1) or MIFC_HSTATS_ROWS (one per grid row of the
+ * box, nrows = j1 - j0, row r is grid row j0 + r); products, a bit mask of MIFC_HSTATS_MOMENTS and MIFC_HSTATS_EXTREMES.
+ * Per field f and level k:
+ *   1. Included cell.  Cell (j, i) is included iff i0 <= i < i1 and j0 <= j < j1; x = fields[f][k][j][i] is defined,
+ *      is_defined(flag == ALL_DEFINED, x, undef) (a stored undef under ALL_DEFINED is a value, as in mifc_hinterp_levels
+ *      rule 3); with minus, y = minus[f][k][j][i] is defined by its own flag; with weight, weight[j][i] is defined by
+ *      fdef_weight.  A caller masks a region by storing undef in weight.
+ *   2. Cell quantities, all in double, each operation rounded on its own, no contraction:
+ *      d = ((double)x - (double)y) - pivot (without minus the first subtraction is absent, d = (double)x - pivot; with
+ *      pivot NULL d = (double)x exactly); w = (double)weight, or 1.0 without a weight; q1 = w * d; q2 = (w * d) * d.  An
+ *      excluded cell contributes w = q1 = q2 = +0.0; because accumulators start at +0.0 this is identical to skipping it.
+ *   3. Row segment sum, the order of every sum W = sum of w, S1 = sum of q1, S2 = sum of q2.  A grid row is cut by
+ *      absolute column into segments of 4096 cells, segment s holding the columns 4096 s .. 4096 s + 4095.  Within a
+ *      segment cell i belongs to partial l = (i / 4) mod 64.  Partial l is the sequential sum, in ascending i, of its
+ *      cells, starting from +0.0: at most 16 trips of four consecutive cells.  The 64 partials are merged by
+ *      for s in 32, 16, 8, 4, 2, 1: P[t] = P[t] + P[t + s] for t < s; the segment sum is P[0].  The mapping depends only on
+ *      the column index, not on the address, the alignment, the box or the staging.
+ *   4. Combination.  ROWS: the result of row r is the sequential sum, ascending, of its segment sums, starting from +0.0.
+ *      AREA: the result is the sequential sum of ALL segment sums of the box rows in row-major order (row j0 segment 0,
+ *      segment 1, ..., then row j0 + 1, ...), starting from +0.0.
+ *   5. N is the exact number of included cells, stored as a double.
+ *   6. Extremes are over d.  MIN is the smallest d of the included cells under the ordered comparison <, starting from
+ *      +inf; IMIN is the smallest flat index j * nx + i within the level among the cells whose d equals it, and MIN is that
+ *      cell's d bit for bit, so -0.0 and +0.0 tie and the first one wins.  MAX and IMAX mirror this with > from -inf.
+ *      Nothing selected gives MIN = +inf, MAX = -inf, IMIN = IMAX = -1.  A NaN, or a d equal to the starting infinity, is
+ *      never selected; a NaN value under ALL_DEFINED makes the sums NaN and is never an extreme.  The definition is
+ *      independent of order (the kernels break ties by index when they merge).
+ *   7. Outputs.  stats is double[nfields][nlev][nrows][8] in the order N, W, S1, S2, MIN, MAX, IMIN, IMAX
+ *      (MIFC_HSTATS_N .. MIFC_HSTATS_IMAX) and lives where memkind says; the four slots of a group that is not requested
+ *      are not written.  Optional mean (a HOST array of nfields pointers, NULL: none; it requires MOMENTS): mean[f] is
+ *      float[nlev][nrows], where memkind says, (float)(pivot + S1 / W), undef where N == 0 or W == 0.0, with
+ *      fdefined_mean[f * nlev + k] = checkDefined(rows left undef, nrows) (a HOST int[nfields * nlev]).
+ *      What a caller derives from stats: the mean pivot + S1 / W; the variance about the mean S2 / W - (S1 / W)^2; the RMSE
+ *      of x - y with pivot 0, sqrt(S2 / W).  When |mean| >> sigma, a second call with pivot = mean removes the
+ *      cancellation; both passes stay on the device.
+ *   8. Refusals.  A refused call returns 0, writes nothing and gives the reason in mifc_last_error(): nlev < 1; nfields
+ *      outside 1..8; nx < 1 or ny < 1; nx * ny > 2^31 - 1; a null pointer that is required; a box that is empty or outside
+ *      the grid; an unknown mode; products == 0 or unknown bits; mean without MOMENTS; an output that overlaps an input or
+ *      another output by byte range; a bad memkind; a call made while a mifc_graph capture is open.
+ * (Restated in numpy in tests/hstats_restate.py.)
+ * Device memory is used where it is (16-byte loads where every row of every batch is on the 16-byte grid, else dwords; the
+ * result is the same): no copies, one synchronisation at the end.  Host memory works at any size: rows are independent up
+ * to rule 4, so the call stages a band of rows of every level at a time, MIFC_HSTATS_CHUNK_MIB of device memory (default
+ * 256), and combines the partial sums of all bands at the end -- bit for bit the result of one device call
+ * (DESIGN.md 4.22).  Not offered: reduction along y only; histograms and percentiles over an area; products of two fields.
+ * mifc_last_hstats_form: the launch shape of the calling thread's last mifc_hstats_levels call, a diagnostic for tests:
+ * "mode=area|rows v=4|1 nf=<fields per launch> w=0|1 minus=0|1 tested=0|1 products=<mask> segs=<segments per row>
+ * blocks=<grid.x> launches=<n> bands=<n>" (launches: of the segment kernel); "" before the first call. */
+enum { MIFC_HSTATS_AREA = 0, MIFC_HSTATS_ROWS = 1 };
+enum { MIFC_HSTATS_MOMENTS = 1, MIFC_HSTATS_EXTREMES = 2 };
+enum { MIFC_HSTATS_N = 0, MIFC_HSTATS_W = 1, MIFC_HSTATS_S1 = 2, MIFC_HSTATS_S2 = 3, MIFC_HSTATS_MIN = 4, MIFC_HSTATS_MAX = 5,
+       MIFC_HSTATS_IMIN = 6, MIFC_HSTATS_IMAX = 7 };
+int mifc_hstats_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* const* minus, const int* fdefined_minus, const double* pivot, const float* weight,
+                       int fdef_weight, const int* box, int mode, int products, double* stats, float* const* mean,
+                       int* fdefined_mean, float undef, int memkind);
+const char* mifc_last_hstats_form(void);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

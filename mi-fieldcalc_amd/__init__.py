@@ -23,7 +23,7 @@ ALL_DEFINED, NONE_DEFINED, SOME_DEFINED = 0, 1, 2  # miutil::ValuesDefined, Fiel
 UNDEF = np.float32(1.0e35)  # miutil::UNDEF, FieldDefined.cc:34
 MEM_HOST, MEM_DEVICE = 0, 1
 
-__all__ = ["Context", "SlabPlan", "Graph", "PreparedCalls", "ALL_DEFINED", "NONE_DEFINED", "SOME_DEFINED", "UNDEF", "classify",
+__all__ = ["Context", "SlabPlan", "Graph", "PreparedCalls", "HstatsResult", "ALL_DEFINED", "NONE_DEFINED", "SOME_DEFINED", "UNDEF", "classify",
            "ensemble_products"]
 
 # mifc_ens_product.stat (include/mifc.h), and the names Context.ensembleStatistics takes for them
@@ -36,6 +36,9 @@ VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max":
 VDERIV_METHODS = {"centred": 0, "weighted": 1}
 # the methods of mifc_hinterp_levels (MIFC_HINTERP_*)
 HINTERP_METHODS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+# the modes and product groups of mifc_hstats_levels (MIFC_HSTATS_*)
+HSTATS_MODES = {"area": 0, "rows": 1}
+HSTATS_PRODUCTS = {"moments": 1, "extremes": 2}
 
 
 def ensemble_products(products):
@@ -260,6 +263,46 @@ def _coord_flags(fdef_coord, coord):
     if fc_.size != int(_Arg(coord).shape[0]):
         raise ValueError("fdef_coord must hold one flag per level")
     return fc_
+
+
+class HstatsResult:
+    """What Context.hstats_levels returns: `stats`, the raw float64 array (nf, nlev, nrows, 8) of mifc_hstats_levels -- a
+    numpy array for host fields, a CUDA tensor for device fields, the leading axis dropped for ONE batch -- with the named
+    views n, w, s1, s2, min, max, imin, imax (the slots of a product group that was not requested hold NaN), `pivot`
+    (float64, shaped like a view without the row axis, or None), and, when the call asked for them, the float32 batch
+    `mean_batch` (nf, nlev, nrows) and its flags `mean_flags` int32 (nf, nlev).  mean(), variance() and rms() are computed
+    in float64 on the host from stats."""
+
+    _SLOTS = ("n", "w", "s1", "s2", "min", "max", "imin", "imax")
+
+    def __init__(self, stats, pivot, mean_batch, mean_flags):
+        self.stats, self.pivot, self.mean_batch, self.mean_flags = stats, pivot, mean_batch, mean_flags
+
+    def __getattr__(self, name):
+        if name in HstatsResult._SLOTS:
+            return self.stats[..., HstatsResult._SLOTS.index(name)]
+        raise AttributeError(name)
+
+    def _host(self, slot):
+        v = self.stats[..., slot]
+        return v.cpu().numpy() if _is_torch(v) else np.asarray(v)
+
+    def mean(self):
+        """pivot + S1 / W, float64 (NaN where W is 0)."""
+        p = 0.0 if self.pivot is None else np.asarray(self.pivot, np.float64)[..., None]
+        with np.errstate(all="ignore"):
+            return p + self._host(2) / self._host(1)
+
+    def variance(self):
+        """S2 / W - (S1 / W)^2, about the mean whatever the pivot; float64."""
+        with np.errstate(all="ignore"):
+            m = self._host(2) / self._host(1)
+            return self._host(3) / self._host(1) - m * m
+
+    def rms(self):
+        """sqrt(S2 / W): with `minus` and no pivot the RMSE of x - y; float64."""
+        with np.errstate(all="ignore"):
+            return np.sqrt(self._host(3) / self._host(1))
 
 
 class Context:
@@ -926,6 +969,84 @@ class Context:
         tests): method as a string, the other keys as ints."""
         form = dict(word.split("=", 1) for word in self._lib.mifc_last_hinterp_form().decode().split())
         return {k: (v if k == "method" else int(v)) for k, v in form.items()}
+
+    # ------------------------------------------ horizontal statistics of level batches (EXTENSION)
+    def hstats_levels(self, fields, minus=None, pivot=None, weight=None, box=None, mode="area", products=("moments", "extremes"), want_mean=False,
+                      fdefined_in=None, fdefined_minus=None, fdef_weight=SOME_DEFINED, undef=UNDEF, out=None):
+        """EXTENSION (include/mifc.h, mifc_hstats_levels): area ("area": one result per field and level) or row-wise
+        ("rows": one per grid row of the box) statistics of level batches, reproducible bit for bit -- the count N, the sums
+        W, S1, S2 of w, w * d and w * d * d (products "moments") and the minimum and maximum of d with the flat index
+        j * nx + i of their first cell (products "extremes"), d = (x - y) - pivot in double.  fields, fdefined_in: as
+        vderiv_fields takes them.  minus: batches y like the fields (bias, RMSE), with fdefined_minus; pivot: float64, one
+        per field and level; weight: (ny, nx), like the fields, a stored undef masks a cell (fdef_weight: its flag);
+        box: (i0, i1, j0, j1), half-open.  products: names or a MIFC_HSTATS_* bit mask.  out: a float64 array / tensor
+        (nf, nlev, nrows, 8) to write into.  Returns an HstatsResult; want_mean adds the float32 batch of means
+        (nf, nlev, nrows) -- reshaped to (nlev, nrows, 1) a level batch for vinterp_* -- and its flags.  With ONE
+        (nlev, ny, nx) batch for `fields` the leading axis is dropped everywhere.  A refused call raises RuntimeError."""
+        code = HSTATS_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+        if isinstance(products, str):
+            products = (products,)
+        mask = int(products) if isinstance(products, (int, np.integer)) else sum({HSTATS_PRODUCTS.get(p, 4) if isinstance(p, str) else int(p) for p in products})
+        one, batches, fa, shape = _level_batches(fields)
+        nlev, ny, nx = shape
+        nf = len(fa)
+        ma = []
+        if minus is not None:
+            _, _, ma, mshape = _level_batches(minus)
+            if len(ma) != nf or mshape != shape:
+                raise ValueError("minus must hold one batch like the fields per field")
+        wa = _Arg(weight, allow_none=True)
+        if weight is not None and tuple(wa.shape) != (ny, nx):
+            raise ValueError("weight must have the shape %s" % ((ny, nx),))
+        bx = None
+        if box is not None:
+            bx = np.ascontiguousarray(np.asarray(box, dtype=np.int32).ravel())
+            if bx.size != 4:
+                raise ValueError("box is (i0, i1, j0, j1)")
+        nrows = 1 if code == 0 else (int(bx[3] - bx[2]) if bx is not None else ny)
+        pv = None
+        if pivot is not None:
+            pv = np.ascontiguousarray(np.broadcast_to(np.asarray(pivot, dtype=np.float64), (nlev,) if one else (nf, nlev)))
+        device = fa[0].device
+        stats_shape = (nf, nlev, max(nrows, 0), 8)
+        if out is None:
+            if device:
+                import torch
+
+                stats = torch.full(stats_shape, float("nan"), dtype=torch.float64, device=batches[0].device)
+            else:
+                stats = np.full(stats_shape, np.nan, np.float64)
+        else:
+            stats = out
+            ok = (_is_torch(out) and out.is_cuda and out.is_contiguous() and str(out.dtype) == "torch.float64") if device else (
+                isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags["C_CONTIGUOUS"])
+            if not ok or tuple(out.shape) not in (stats_shape, stats_shape[1:] if one else stats_shape):
+                raise ValueError("out must be a contiguous float64 array (host fields) or CUDA tensor (device fields) of shape %s" % (stats_shape,))
+        stats_addr = stats.data_ptr() if _is_torch(stats) else stats.ctypes.data
+        mean = ma_out = mean_table = mfd = None
+        if want_mean:
+            mean = _empty_like(batches[0], (nf, nlev, max(nrows, 0)))
+            ma_out = _Arg(mean, output=True)
+            mean_table = (ctypes.c_void_p * nf)(*[ma_out.addr + f * nlev * nrows * 4 for f in range(nf)])
+            mfd = np.zeros((nf, nlev), np.int32)
+        mk = _memkind(fa + ma + [wa] + ([ma_out] if want_mean else []), self.device)
+        self._bind_stream(mk)
+        table = (ctypes.c_void_p * nf)(*[a.addr for a in fa])
+        mtable = (ctypes.c_void_p * nf)(*[a.addr for a in ma]) if ma else None
+        args = [nx, ny, nlev, ctypes.addressof(table), _level_flags(fdefined_in, nf, nlev), nf, ctypes.addressof(mtable) if ma else None,
+                _level_flags(fdefined_minus, nf, nlev) if ma else None, pv, wa.addr, int(fdef_weight), bx, code, mask, stats_addr,
+                ctypes.addressof(mean_table) if want_mean else None, mfd, float(undef), mk]
+        if not self._call("mifc_hstats_levels", args):
+            raise RuntimeError("mifc_hstats_levels: " + self.last_error())
+        if one:
+            stats = stats.reshape(stats_shape[1:])
+        return HstatsResult(stats, pv, None if mean is None else (mean[0] if one else mean), None if mfd is None else (mfd[0] if one else mfd))
+
+    def last_hstats_form(self):
+        """The launch shape of this thread's last hstats_levels call as a dict (mifc_last_hstats_form; a diagnostic for
+        tests): mode as a string, the other keys as ints."""
+        form = dict(word.split("=", 1) for word in self._lib.mifc_last_hstats_form().decode().split())
+        return {k: (v if k == "mode" else int(v)) for k, v in form.items()}
 
     # ------------------------------------------ vector pairs rotated, on the grid and while sampling (EXTENSION)
     @staticmethod

@@ -140,6 +140,9 @@ SIGNATURES = {
     "mifc_vrotate_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_last_vrotate_form": ("s", []),
     "mifc_hinterp_vector_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "p", "p", "i", "i", "p", "pi", "f", "i"]),
+    # EXTENSION: horizontal statistics of level batches (fields, minus, mean: host tables of pointers; pivot, box: host arrays; stats: double)
+    "mifc_hstats_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "p", "i", "pi", "i", "i", "p", "p", "pi", "f", "i"]),
+    "mifc_last_hstats_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

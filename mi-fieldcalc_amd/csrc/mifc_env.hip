@@ -54,6 +54,7 @@ void env_reload()
   e.vlayer_chunk_mib = positive_int("MIFC_VLAYER_CHUNK_MIB");
   e.vderiv_chunk_mib = positive_int("MIFC_VDERIV_CHUNK_MIB");
   e.hinterp_chunk_mib = positive_int("MIFC_HINTERP_CHUNK_MIB");
+  e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
   e.hinterp_level_chunk = positive_int("MIFC_HINTERP_LEVEL_CHUNK");
   e.derived_blocks = positive_int("MIFC_DERIVED_BLOCKS");
   e.derived_pipe = not_zero("MIFC_DERIVED_PIPE") ? 1 : 0;

@@ -520,6 +520,61 @@ struct VrotatePlan
 VrotatePlan vrotate_plan(int cells, int nlev, int vec4 = 1);
 hipError_t launch_vrotate(const VrotateParams& prm, hipStream_t stream);
 
+// ------------------------------------ horizontal statistics of level batches (mifc_hstats.hip), EXTENSION
+// Two kernels (rules 1-7 of mifc_hstats_levels, include/mifc.h).  The segment kernel: a wave owns one (row, segment) of up
+// to HSTATS_PASS fields -- the columns [4096 s, 4096 s + 4096) of one grid row, cut to the box -- and walks the levels
+// blockIdx.y, + gridDim.y, ...; lane l owns the cells with (i / 4) mod 64 == l, 16 trips of four consecutive cells at most,
+// loaded as one 16-byte access (vec4: every row of every plane on the 16-byte grid) or as four dwords.  The planes hold
+// the rows [.., ..) of the grid that the caller staged: row r of the launch is row plane_row0 + r of the planes, grid row
+// grid_row0 + r, row part_row0 + r of the box.  Level k of a field lies at fields[f] + k * stride, of minus[f] alike;
+// weight is one plane.  lev_bits[k] bit f0 + f: field f of the launch is flagged ALL_DEFINED there, bit
+// HSTATS_MINUS_BIT + f0 + f: its minus batch is; weight_all: fdef_weight == ALL_DEFINED; tested == 0: every flag of the
+// call is ALL_DEFINED and no value is tested.  pivot: double[call fields][nlev] on the device.  The wave's eight numbers
+// N, W, S1, S2, MIN, MAX, IMIN, IMAX of every field go to
+//   part[((((f0 + f) * nlev + k) * box_rows + part_row0 + r) * segs + (s - seg0)) * 8 ..]   (the requested groups only).
+// The combine kernel: a lane owns one (field, level, result row, slot) and walks its partials in the order of rule 4; it
+// writes stats, and with mean[] given the float mean and, per row left undef, one count into n_undefined[f * nlev + k].
+const int HSTATS_MAX_FIELDS = 8, HSTATS_PASS = 4, HSTATS_SEGMENT = 4096, HSTATS_TRIP = 256, HSTATS_MINUS_BIT = 8;
+const int HSTATS_AREA = 0, HSTATS_ROWS = 1, HSTATS_MOMENTS = 1, HSTATS_EXTREMES = 2;
+struct HstatsParams
+{
+  int nfields; // of this launch, 1 .. HSTATS_PASS
+  int f0;      // the call's field of the launch's field 0
+  int nx, nlev;
+  int i0, i1;                                         // the box's columns
+  int rows, plane_row0, grid_row0, part_row0, box_rows; // see above
+  int seg0, segs;                                     // the first segment that the box touches, how many it touches
+  int products;                                       // HSTATS_MOMENTS | HSTATS_EXTREMES
+  int tested, weight_all, vec4;
+  int level_blocks; // grid.y, the stride of a workgroup's walk over the levels (set by launch_hstats_segments from hstats_plan)
+  float undef;
+  long stride;
+  const float* fields[HSTATS_PASS];
+  const float* minus[HSTATS_PASS]; // all null: none
+  const float* weight;             // null: none
+  const unsigned int* lev_bits;
+  const double* pivot;
+  double* part;
+};
+struct HstatsPlan
+{
+  int blocks, level_blocks; // grid.x: four (row, segment) units per workgroup; grid.y
+};
+HstatsPlan hstats_plan(int rows, int segs, int nlev);
+hipError_t launch_hstats_segments(const HstatsParams& prm, hipStream_t stream);
+struct HstatsCombineParams
+{
+  int nfields, nlev, box_rows, segs; // of the call
+  int mode, products;
+  float undef;
+  const double* part;
+  const double* pivot;
+  double* stats;                  // [nfields][nlev][nrows][8], nrows = 1 (AREA) or box_rows
+  float* mean[HSTATS_MAX_FIELDS]; // [nlev][nrows] each, or all null
+  u64* n_undefined;
+};
+hipError_t launch_hstats_combine(const HstatsCombineParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
