@@ -847,6 +847,20 @@ unsigned long long mifc_stencil_count_domain(int op, int nx, int ny);
  * and for the operators with launchers of their own.  The tests use it to check that a case reaches the kernel it is
  * meant for; nothing on the data path reads it.  The string is static. */
 const char* mifc_last_stencil_form(void);
+/* Diagnostic: how the calling thread's last synchronous level-batch call that can stream a host-memory batch through the
+ * device in chunks (mifc_vortdiv_levels, mifc_stencil_levels, mifc_stencil_levels_ex, mifc_hlevel_derived_levels,
+ * mifc_hlevel_derived_batch and the single-field stencil entries, which share their driver) was run: the number of chunks,
+ * and in *levels_per_chunk (NULL allowed) the levels per chunk; 0 and 0 when the batch was staged whole (device memory, a
+ * batch below the threshold, MIFC_HOST_PIPELINE=0, a request the pipeline does not carry: advection and the other
+ * operators of mifc_stencil_levels_ex, five outputs of the derived batch) or the call was refused.  The
+ * tests use it to check that a case went through the pipeline; nothing on the data path reads it. */
+int mifc_last_host_chunks(int* levels_per_chunk);
+/* The chunking policy of that pipeline for a batch of nlev fields of n cells: the levels per chunk, 0 = staged whole.
+ * By default batches from 64 MiB per field are cut into chunks of at most 32 MiB per field (MIFC_HOST_CHUNK_MIB) and
+ * nlev / 4 levels; MIFC_HOST_PIPE_MIN_KIB (KiB per field) replaces the threshold, MIFC_HOST_CHUNK_LEVELS sets the levels
+ * per chunk (clamped to nlev, no nlev / 4 cap).  Reads the snapshot of the environment that mifc_create and
+ * mifc_reload_env take; needs no context and no device. */
+int mifc_host_chunk_levels(size_t n, int nlev);
 /* Diagnostic: the launch shape of the calling thread's last elementwise (vectorabs, *leveltemp, *levelhum, cvhum, momentum
  * coordinates), catalogue (the other pointwise operators) or fused derived-batch launch, as "key=value" words:
  *   family=ewise|pointwise|derived  op=<kernel instantiation>  form=vector|scalar (four cells per lane | one)

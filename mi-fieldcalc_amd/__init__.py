@@ -1451,6 +1451,13 @@ class Context:
         """The kernel form this thread's last stencil launch took (mifc_last_stencil_form; a diagnostic for tests)."""
         return self._lib.mifc_last_stencil_form().decode()
 
+    def last_host_chunks(self):
+        """(number of chunks, levels per chunk) of this thread's last synchronous level-batch call from host memory; (0, 0) when
+        the batch was staged whole (mifc_last_host_chunks; a diagnostic for tests)."""
+        per_chunk = ctypes.c_int(0)
+        nchunks = self._lib.mifc_last_host_chunks(ctypes.addressof(per_chunk))
+        return int(nchunks), int(per_chunk.value)
+
     def last_pointwise_form(self):
         """The launch shape of this thread's last elementwise, catalogue or derived-batch launch as a dict
         (mifc_last_pointwise_form; a diagnostic for tests): family, form, inst as strings, the other keys as ints."""

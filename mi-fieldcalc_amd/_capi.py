@@ -160,6 +160,8 @@ SIGNATURES = {
     "mifc_stencil_levels_enqueue": ("i", ["ctx", "i", "i", "i", "i", "p", "p", "p", "p", "p", "p", "p", "pi", "f", "pu"]),
     "mifc_stencil_count_domain": ("u64", ["i", "i", "i"]),
     "mifc_last_stencil_form": ("s", []),
+    "mifc_last_host_chunks": ("i", ["pi"]),
+    "mifc_host_chunk_levels": ("i", ["z", "i"]),
     "mifc_last_pointwise_form": ("s", []),
     "mifc_stencil_levels_ex": ("i", ["ctx", "i", "i", "i", "i", "p", "p", "p", "p", "p", "p", "p", "f", "i", "p", "p", "pi", "f", "i"]),
     "mifc_vortdiv_levels_enqueue": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "p", "p", "p", "pi", "f", "pu"]),

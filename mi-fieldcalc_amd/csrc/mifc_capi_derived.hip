@@ -155,6 +155,7 @@ void derived_flags(const u64* cnt, int nlev, size_t n, const DerivedRequest& rq,
 int derived_sync(mifc_ctx* c, int nx, int ny, int nlev, const DerivedRequest& rq0, const int* fdef_wind, const int* fdef_thermo, int* fdef_ff,
                  int* fdef_temp, int* fdef_hum, int* fdef_hum2, int* fdef_dd, float undef, int memkind)
 {
+  mifc::hostpipe_note_chunks(0, 0); // mifc_last_host_chunks: hostpipe_run() reports what it does
   if (nlev < 1 || nx * ny <= 0)
     return 0;
   if (!cells_in_fours(c, nx, ny, "mifc_hlevel_derived_batch"))

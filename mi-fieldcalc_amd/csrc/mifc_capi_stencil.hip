@@ -199,6 +199,7 @@ int prepare_levels(mifc_ctx* c, mifc::StencilParams& P, const int* fdefined, u64
 // ---- single-field / batched stencil driver ---------------------------------
 int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, float undef, int memkind)
 {
+  mifc::hostpipe_note_chunks(0, 0); // mifc_last_host_chunks: hostpipe_run() reports what it does
   if (sc.nx < 3 || sc.ny < 3 || sc.nlev < 1)
     return 0;
   const size_t n = (size_t)sc.nx * sc.ny;
@@ -634,6 +635,7 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
                            float* out1, int* fdefined, float undef, int memkind)
 {
   CTX_OR_FAIL(c);
+  mifc::hostpipe_note_chunks(0, 0); // (the two-stage operators and the filter stage their batch whole and may not reach run_stencil)
   if (op != MIFC_OP_ADVECTION && op != MIFC_OP_TFP && op != MIFC_OP_QVECTOR && op != MIFC_OP_SHAPIRO2)
     return mifc_stencil_levels(c, op, nx, ny, nlev, f0, f1, xmapr, ymapr, fcoriolis, out0, out1, fdefined, undef, memkind);
   if (nx < 3 || ny < 3 || nlev < 1 || !f0 || !out0 || !fdefined)
@@ -862,6 +864,16 @@ int mifc_vortdiv_ff_levels_enqueue(mifc_ctx* c, int nx, int ny, int nlev, const 
 const char* mifc_last_stencil_form(void)
 {
   return mifc::last_form();
+}
+
+int mifc_last_host_chunks(int* levels_per_chunk)
+{
+  return mifc::hostpipe_last_chunks(levels_per_chunk);
+}
+
+int mifc_host_chunk_levels(size_t n, int nlev)
+{
+  return mifc::hostpipe_chunk_levels(n, nlev);
 }
 
 unsigned long long mifc_stencil_count_domain(int op, int nx, int ny)

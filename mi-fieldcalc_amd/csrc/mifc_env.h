@@ -20,6 +20,8 @@ struct Env
   int fused2_band = 0;            // MIFC_FUSED2_BAND (> 0 overrides the band height of the fused two-stage kernels)
   int host_threads = 0;           // MIFC_HOST_THREADS (> 0)
   int host_chunk_mib = 0;         // MIFC_HOST_CHUNK_MIB (> 0)
+  int host_pipe_min_kib = 0;      // MIFC_HOST_PIPE_MIN_KIB (> 0 replaces the 64 MiB per field from which a host-memory level batch is pipelined; tests)
+  int host_chunk_levels = 0;      // MIFC_HOST_CHUNK_LEVELS (> 0: levels per chunk of the host pipeline, before MIFC_HOST_CHUNK_MIB and without the nlev / 4 cap; tests)
   int quantile_chunk_mib = 0;     // MIFC_QUANTILE_CHUNK_MIB (> 0): device staging of a host-memory mifc_ensembleQuantiles call (default 256)
   int ensemble_chunk_mib = 0;     // MIFC_ENSEMBLE_CHUNK_MIB (> 0): device staging of a host-memory mifc_ensemble_levels call (default 256)
   int vinterp_chunk_mib = 0;      // MIFC_VINTERP_CHUNK_MIB (> 0): device staging of a host-memory mifc_vinterp_* call, a band of rows at a time (default 256)

@@ -48,6 +48,8 @@ void env_reload()
   e.fused2_band = positive_int("MIFC_FUSED2_BAND");
   e.host_threads = positive_int("MIFC_HOST_THREADS");
   e.host_chunk_mib = positive_int("MIFC_HOST_CHUNK_MIB");
+  e.host_pipe_min_kib = positive_int("MIFC_HOST_PIPE_MIN_KIB");
+  e.host_chunk_levels = positive_int("MIFC_HOST_CHUNK_LEVELS");
   e.quantile_chunk_mib = positive_int("MIFC_QUANTILE_CHUNK_MIB");
   e.ensemble_chunk_mib = positive_int("MIFC_ENSEMBLE_CHUNK_MIB");
   e.vinterp_chunk_mib = positive_int("MIFC_VINTERP_CHUNK_MIB");

@@ -43,7 +43,14 @@ bool hostpipe_run(HostPipe* hp, size_t n, int nlev, int n_in, const float* const
                   std::string* err);
 
 // how many levels go into one chunk for fields of n cells (0: batch too small to pipeline)
+// (MIFC_HOST_PIPE_MIN_KIB replaces the 64 MiB per field below which nothing is pipelined, MIFC_HOST_CHUNK_LEVELS sets the
+// levels per chunk whatever the chunk size and the nlev / 4 cap say: the tests' way in for small batches)
 int hostpipe_chunk_levels(size_t n, int nlev);
+
+// What mifc_last_host_chunks reports for the calling thread: the entries that can pipe note (0, 0) on entry,
+// hostpipe_run() the number of chunks and the levels per chunk it runs with.
+void hostpipe_note_chunks(int nchunks, int levels_per_chunk);
+int hostpipe_last_chunks(int* levels_per_chunk);
 
 } // namespace mifc
 

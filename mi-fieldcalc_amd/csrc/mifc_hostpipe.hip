@@ -1,5 +1,6 @@
 // mifc_hostpipe.hip -- see mifc_hostpipe.h.
 #include "mifc_hostpipe.h"
+#include "mifc_copypool.h"
 #include "mifc_env.h"
 
 #include <atomic>
@@ -16,83 +17,6 @@
 namespace mifc {
 
 namespace {
-
-// A handful of threads that do nothing but memcpy between the caller's
-// pageable memory and the pinned staging buffers.  copy() may be called from
-// two threads at once (the feeding and the draining side of the pipeline).
-class CopyPool
-{
-public:
-  explicit CopyPool(int nthreads)
-  {
-    for (int t = 0; t < nthreads; ++t)
-      workers_.emplace_back([this] { work(); });
-  }
-  ~CopyPool()
-  {
-    {
-      std::lock_guard<std::mutex> g(m_);
-      stop_ = true;
-    }
-    cv_job_.notify_all();
-    for (auto& t : workers_)
-      t.join();
-  }
-  void copy(void* dst, const void* src, size_t bytes)
-  {
-    const size_t slice = size_t(2) << 20;
-    int pending = 0;
-    {
-      std::lock_guard<std::mutex> g(m_);
-      for (size_t off = 0; off < bytes; off += slice) {
-        Slice s;
-        s.dst = static_cast<char*>(dst) + off;
-        s.src = static_cast<const char*>(src) + off;
-        s.bytes = (off + slice > bytes) ? bytes - off : slice;
-        s.pending = &pending;
-        jobs_.push_back(s);
-        ++pending;
-      }
-    }
-    cv_job_.notify_all();
-    std::unique_lock<std::mutex> g(m_);
-    cv_done_.wait(g, [&] { return pending == 0; });
-  }
-
-private:
-  struct Slice
-  {
-    char* dst;
-    const char* src;
-    size_t bytes;
-    int* pending; // guarded by m_
-  };
-  void work()
-  {
-    for (;;) {
-      Slice s;
-      {
-        std::unique_lock<std::mutex> g(m_);
-        cv_job_.wait(g, [&] { return stop_ || !jobs_.empty(); });
-        if (jobs_.empty())
-          return;
-        s = jobs_.front();
-        jobs_.pop_front();
-      }
-      std::memcpy(s.dst, s.src, s.bytes);
-      {
-        std::lock_guard<std::mutex> g(m_);
-        if (--*s.pending == 0)
-          cv_done_.notify_all();
-      }
-    }
-  }
-  std::vector<std::thread> workers_;
-  std::mutex m_;
-  std::condition_variable cv_job_, cv_done_;
-  std::deque<Slice> jobs_;
-  bool stop_ = false;
-};
 
 int copy_threads()
 {
@@ -180,8 +104,13 @@ void hostpipe_destroy(HostPipe* hp)
 int hostpipe_chunk_levels(size_t n, int nlev)
 {
   const size_t field_bytes = n * sizeof(float);
-  if (field_bytes == 0 || (size_t)nlev * field_bytes < (size_t(64) << 20))
-    return 0; // under 64 MiB per field the ramp-up costs more than the overlap gains
+  size_t min_bytes = size_t(64) << 20; // under 64 MiB per field the ramp-up costs more than the overlap gains
+  if (env().host_pipe_min_kib > 0)
+    min_bytes = (size_t)env().host_pipe_min_kib << 10;
+  if (field_bytes == 0 || nlev < 1 || (size_t)nlev * field_bytes < min_bytes)
+    return 0;
+  if (env().host_chunk_levels > 0) // tests: any number of chunks, one included
+    return env().host_chunk_levels < nlev ? env().host_chunk_levels : nlev;
   size_t chunk_mib = 32; // per field and chunk
   if (env().host_chunk_mib > 0)
     chunk_mib = (size_t)env().host_chunk_mib;
@@ -193,6 +122,23 @@ int hostpipe_chunk_levels(size_t n, int nlev)
   return lev < 1 ? 1 : (int)lev;
 }
 
+namespace {
+thread_local int t_last_chunks = 0, t_last_chunk_levels = 0;
+}
+
+void hostpipe_note_chunks(int nchunks, int levels_per_chunk)
+{
+  t_last_chunks = nchunks;
+  t_last_chunk_levels = levels_per_chunk;
+}
+
+int hostpipe_last_chunks(int* levels_per_chunk)
+{
+  if (levels_per_chunk)
+    *levels_per_chunk = t_last_chunk_levels;
+  return t_last_chunks;
+}
+
 bool hostpipe_run(HostPipe* hp, size_t n, int nlev, int n_in, const float* const* in, int n_out, float* const* out, const ChunkLaunch& launch,
                   std::string* err)
 {
@@ -201,6 +147,7 @@ bool hostpipe_run(HostPipe* hp, size_t n, int nlev, int n_in, const float* const
     std::snprintf(buf, sizeof buf, "host pipeline: %s: %s", what, hipGetErrorString(e));
     if (err)
       *err = buf;
+    hostpipe_note_chunks(0, 0); // a call that fails reports no chunks
     return false;
   };
   if (n_in > MAXF || n_out > MAXF)
@@ -246,6 +193,7 @@ bool hostpipe_run(HostPipe* hp, size_t n, int nlev, int n_in, const float* const
     }
   }
   const int nchunks = (nlev + L - 1) / L;
+  hostpipe_note_chunks(nchunks, L);
 
   // feeder (this thread) <-> drainer hand-over
   std::mutex m;

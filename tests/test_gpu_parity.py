@@ -431,6 +431,8 @@ def test_vortdiv_levels_host_pipeline(gpu_ctx, oracle, nlev, want, mifc_env):
     u, v, xm, ym, flags = _levels_inputs(nx, ny, nlev, 31337)
     kw = dict(fdefined=flags, want=want)
     (rv, dv), fo = gpu_ctx.vortdiv_levels(u, v, xm, ym, **kw)
+    if not gpu_util.run_is_forced():  # the default policy: 5 chunks of nlev / 4 levels, the last one ragged
+        assert gpu_ctx.last_host_chunks() == (5, nlev // 4)
     mifc_env("MIFC_HOST_PIPELINE", "0")
     (rv0, dv0), fo0 = gpu_ctx.vortdiv_levels(u, v, xm, ym, **kw)
     assert np.array_equal(fo, fo0)
@@ -599,6 +601,8 @@ def test_hlevel_derived_levels_host_pipeline(gpu_ctx, want, mifc_env):
         t[l] = synth.sprinkle_undef(t[l], 60 + l, 0.02)
     kw = dict(fdef_wind=fw, fdef_thermo=ft, want=want)
     res, flags = gpu_ctx.hlevel_derived_levels(u, v, t, q, ps, a, b, **kw)
+    if not gpu_util.run_is_forced():  # the default policy: 5 chunks of nlev / 4 levels, the last one ragged
+        assert gpu_ctx.last_host_chunks() == (5, nlev // 4)
     mifc_env("MIFC_HOST_PIPELINE", "0")
     res0, flags0 = gpu_ctx.hlevel_derived_levels(u, v, t, q, ps, a, b, **kw)
     for k in want:
