@@ -1,0 +1,19 @@
+"""The constants of the Python front: a leaf module, so that the method families can share them without importing the
+package back."""
+import numpy as np
+
+ALL_DEFINED, NONE_DEFINED, SOME_DEFINED = 0, 1, 2  # miutil::ValuesDefined, FieldDefined.h:41
+UNDEF = np.float32(1.0e35)  # miutil::UNDEF, FieldDefined.cc:34
+MEM_HOST, MEM_DEVICE = 0, 1
+
+# mifc_ens_product.stat (include/mifc.h), and the names Context.ensembleStatistics takes for them
+ENS_SUM, ENS_MEAN, ENS_STDDEV, ENS_EXTREME, ENS_PROBABILITY = 0, 1, 2, 3, 4
+# the product codes of mifc_vlayer_* (include/mifc.h, MIFC_VLAYER_*) and the names Context.vlayer_* takes for them
+VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max": 5, "coord_of_min": 6}
+# the methods of mifc_vderiv_* (MIFC_VDERIV_*)
+VDERIV_METHODS = {"centred": 0, "weighted": 1}
+# the methods of mifc_hinterp_levels (MIFC_HINTERP_*)
+HINTERP_METHODS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+# the modes and product groups of mifc_hstats_levels (MIFC_HSTATS_*)
+HSTATS_MODES = {"area": 0, "rows": 1}
+HSTATS_PRODUCTS = {"moments": 1, "extremes": 2}
