@@ -843,9 +843,16 @@ unsigned long long mifc_stencil_count_domain(int op, int nx, int ny);
 
 /* Diagnostic: the kernel form the calling thread's last stencil launch took -- "wind_split", "wind_split_ragged",
  * "wind_split_ff", "wind_levelwalk", "wind_rows", "wind_oneshot", "wind_oneshot_tiles", "scalar_split",
- * "scalar_split_ragged", "scalar_levelwalk", "scalar_rows", "scalar_oneshot", "advection_split", "advection_split_ragged", "advection_oneshot", "flat4", "cell"; "" before the first launch
- * and for the operators with launchers of their own.  The tests use it to check that a case reaches the kernel it is
- * meant for; nothing on the data path reads it.  The string is static. */
+ * "scalar_split_ragged", "scalar_levelwalk", "scalar_rows", "scalar_oneshot", "advection_split", "advection_split_ragged", "advection_oneshot", "flat4", "cell"; "" before the first launch.
+ * thermalFrontParameter, plevelqvector and shapiro2_filter (single fields and mifc_stencil_levels_ex batches) report the
+ * ROUTE of the call instead, set as its last act:
+ *   "fused2"            the one-launch two-stage kernel, no level repaired
+ *   "fused2_redo"       the same, and at least one level of thermalFrontParameter went again pass by pass (.cc:2286)
+ *   "two_stage_passes"  thermalFrontParameter's two passes / plevelqvector's three
+ *   "shapiro_fused"     the filter's four sweeps in one launch
+ *   "shapiro_sweeps"    the filter's masks plus four sweep launches
+ * The tests use it to check that a case reaches the kernel it is meant for; nothing on the data path reads it.  The
+ * string is static. */
 const char* mifc_last_stencil_form(void);
 /* Diagnostic: how the calling thread's last synchronous level-batch call that can stream a host-memory batch through the
  * device in chunks (mifc_vortdiv_levels, mifc_stencil_levels, mifc_stencil_levels_ex, mifc_hlevel_derived_levels,

@@ -580,60 +580,6 @@ int mifc_values2classes(mifc_ctx* c, int nx, int ny, const float* fvalue, float*
   return run_pointwise(c, nx, ny, pc, fclass, fdefined, memkind);
 }
 
-// ------------------------------------------------------------- second-order Shapiro filter
-// FieldCalculations.cc:2076-2179: four sweeps between the output and a scratch field; `field`
-// and `fsmooth` may be the same array; the flag always becomes ALL_DEFINED (:2176).
-int mifc_shapiro2_filter(mifc_ctx* c, int nx, int ny, const float* field, float* fsmooth, int* fdefined, float undef, int memkind)
-{
-  CTX_OR_FAIL(c);
-  if (nx < 3 || ny < 3 || !field || !fsmooth) // :2093
-    return 0;
-  const size_t n = (size_t)nx * (size_t)ny;
-  if (n > 0x7fffffffu)
-    return 0;
-  Staging st(c, memkind);
-  const float* d_in = st.in(field, n);
-  float* d_out = st.out(fsmooth, n);
-  const bool all = (*fdefined == MIFC_ALL_DEFINED);
-  float* d_sweep = static_cast<float*>(st.scratch(n * sizeof(float)));
-  if (!st.ok())
-    return 0;
-  {
-    // the four sweeps in one launch; it needs source and destination to be different arrays, so an
-    // in-place call goes through the scratch field and is copied back
-    // MIFC_SHAPIRO_FUSED=0: the four-launch path (A/B measurements, tests)
-    float* d_dst = (d_out != d_in) ? d_out : d_sweep;
-    if (mifc::env().shapiro_fused && mifc::shapiro2_fused_supported(nx, ny, d_in, d_dst)) {
-      MIFC_LAUNCH(c, mifc::launch_shapiro2_fused(nx, ny, all ? 1 : 0, undef, d_in, d_dst, c->stream));
-      if (d_dst != d_out)
-        MIFC_HIP(c, hipMemcpyAsync(d_out, d_dst, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      if (!st.finish())
-        return 0;
-      *fdefined = MIFC_ALL_DEFINED;
-      return 1;
-    }
-  }
-  unsigned char* d_masks = all ? nullptr : static_cast<unsigned char*>(st.scratch(2 * n));
-  if (!st.ok())
-    return 0;
-  if (d_out != d_in)
-    MIFC_HIP(c, hipMemcpyAsync(d_out, d_in, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  mifc::ShapiroParams P;
-  P.nx = nx;
-  P.ny = ny;
-  P.all_defined = all ? 1 : 0;
-  P.undef = undef;
-  P.f1 = d_out;
-  P.f2 = d_sweep;
-  P.mask_x = d_masks;
-  P.mask_y = all ? nullptr : d_masks + n;
-  MIFC_LAUNCH(c, mifc::launch_shapiro2(P, c->stream));
-  if (!st.finish())
-    return 0;
-  *fdefined = MIFC_ALL_DEFINED;
-  return 1;
-}
-
 // ------------------------------------------------------------- vessel icing (closed-form models)
 static int vessel_icing(mifc_ctx* c, int model, int nx, int ny, const float* airtemp, const float* seatemp, const float* u, const float* v,
                         const float* sal, const float* aice, float* icing, int* fdefined, float undef, int memkind)

@@ -1,13 +1,10 @@
 // mifc_capi_stencil.hip -- the extern "C" boundary of the stencil operators (mifc_stencil*.hip, mifc_vortdiv.hip,
-// mifc_fused2.hip, mifc_shapiro.hip, mifc_advection.hip): the single-field entries, the level batches in their synchronous
-// and *_enqueue forms and the row-slab launches, on ONE preparation path: a StencilCall becomes StencilParams in
-// stencil_params(), the per-level flags and counters are put in place by prepare_levels(), and the multi-pass drivers of
-// thermalFrontParameter, plevelqvector and shapiro2_filter run their passes through run_stencil().
+// mifc_advection.hip): the single-field entries, the level batches in their synchronous and *_enqueue forms and the
+// row-slab launches, on ONE preparation path: a StencilCall becomes StencilParams in
+// stencil_params() and the per-level flags and counters are put in place by prepare_levels().  The two-stage operators and
+// the Shapiro filter live in mifc_capi_twostage.hip; their passes come back here through run_stencil().
 
-#include <cmath>
 #include <cstring>
-#include <string>
-#include <vector>
 
 #include "mifc_stencil_host.h"
 
@@ -196,8 +193,10 @@ int prepare_levels(mifc_ctx* c, mifc::StencilParams& P, const int* fdefined, u64
   return 1;
 }
 
+} // namespace
+
 // ---- single-field / batched stencil driver ---------------------------------
-int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, float undef, int memkind)
+int mifc_host::run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, float undef, int memkind)
 {
   mifc::hostpipe_note_chunks(0, 0); // mifc_last_host_chunks: hostpipe_run() reports what it does
   if (sc.nx < 3 || sc.ny < 3 || sc.nlev < 1)
@@ -275,8 +274,6 @@ int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined /* [nlev] */, 
   }
   return 1;
 }
-
-} // namespace
 
 extern "C" {
 
@@ -373,193 +370,6 @@ int mifc_jacobian(mifc_ctx* c, int nx, int ny, const float* field1, const float*
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
 
-// One launch of mifc_fused2.hip on device pointers.  Returns 0 on error, 1 when
-// the result stands (flag written), 2 when the caller has to take the
-// multi-pass path after all (see the thermalFrontParameter note below).
-static int run_fused2(mifc_ctx* c, mifc::Fused2Params& P, int* fdefined)
-{
-  if (!ensure_levels(c, 4) || !pinned_acquire(c))
-    return 0;
-  P.counts = c->d_counts;
-  P.check = (*fdefined != MIFC_ALL_DEFINED) ? 1 : 0;
-  if (!mifc::fused2_supported(P))
-    return 2;
-  MIFC_HIP(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(u64), c->stream));
-  MIFC_LAUNCH(c, mifc::launch_fused2(P, c->stream));
-  MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  MIFC_HIP(c, hipStreamSynchronize(c->stream));
-  const u64* n = pinned_counts(c);
-  // thermalFrontParameter's second pass tests its inputs only if the first pass
-  // left something undefined (:2286).  The kernel ran it tested; if the first
-  // pass turned out clean AND the test rejected a cell the untested loop would
-  // have computed (a NaN gradient from defined inputs), the result differs.
-  if (P.op == mifc::F2_TFP && P.check && n[0] == 0 && n[2] != 0)
-    return 2;
-  *fdefined = mifc_classify(n[1], (u64)P.nx * (u64)P.ny - 2 * (u64)P.nx); // :2303, :590
-  return 1;
-}
-
-// the request of a one-launch two-stage operator; the scalars or per-level tables of the Q-vector are the caller's
-static mifc::Fused2Params fused2_params(int op, int nx, int ny, const float* a, const float* t, const float* xm, const float* ym, const float* fc,
-                                        float* out, float undef)
-{
-  mifc::Fused2Params F;
-  std::memset(&F, 0, sizeof F);
-  F.op = op;
-  F.nx = nx;
-  F.ny = ny;
-  F.a = a;
-  F.t = t;
-  F.xmapr = xm;
-  F.ymapr = ym;
-  F.fcoriolis = fc;
-  F.out = out;
-  F.undef = undef;
-  return F;
-}
-
-static bool fused2_enabled()
-{
-  return mifc::env().fused2; // MIFC_FUSED2=0: always the multi-pass path (A/B measurements, tests)
-}
-
-// thermalFrontParameter pass by pass on device pointers: |grad T| into the context's scratch, then the
-// front parameter; the second pass takes its "all defined" from the flag the first one returned (:2286)
-// Device pointers; nlev levels at once (fields nx * ny floats apart, the intermediate batch in the context's scratch): each
-// pass is ONE launch over the levels, the second takes every level's "all defined" from what the first returned for it.
-static int tfp_two_passes(mifc_ctx* c, int nx, int ny, const float* d_tx, const float* d_xm, const float* d_ym, float* d_out, int* fdefined,
-                          float undef, int nlev = 1)
-{
-  const size_t n = (size_t)nx * ny;
-  Staging st(c, MIFC_MEM_DEVICE);
-  float* d_absdelt = static_cast<float*>(st.scratch(n * (size_t)nlev * sizeof(float)));
-  if (!st.ok())
-    return 0;
-  const StencilCall pass1 = {mifc::ST_GRAD_ABS, nx, ny, nlev, d_tx, nullptr, d_xm, d_ym, nullptr, d_absdelt, nullptr};
-  if (!run_stencil(c, pass1, fdefined, undef, MIFC_MEM_DEVICE))
-    return 0;
-  const StencilCall pass2 = {mifc::ST_TFP, nx, ny, nlev, d_tx, d_absdelt, d_xm, d_ym, nullptr, d_out, nullptr};
-  return run_stencil(c, pass2, fdefined, undef, MIFC_MEM_DEVICE);
-}
-
-// thermalFrontParameter, FieldCalculations.cc:2266-2309.  One fused launch where
-// the grid allows it; otherwise two passes with an intermediate |grad T| field
-// that lives in the context's scratch.  The second pass takes its "all defined"
-// from the flag the first pass returned (:2286).
-int mifc_thermalFrontParameter(mifc_ctx* c, int nx, int ny, const float* tx, const float* xmapr, const float* ymapr, float* tfp, int* fdefined,
-                               float undef, int memkind)
-{
-  CTX_OR_FAIL(c);
-  if (nx < 3 || ny < 3) // gradient() :2004
-    return 0;
-  const size_t n = (size_t)nx * ny;
-  Staging st(c, memkind);
-  // bring the inputs to the device once; both passes then run on device pointers
-  const float* d_tx = st.in(tx, n);
-  const float* d_xm = st.in(xmapr, n);
-  const float* d_ym = st.in(ymapr, n);
-  float* d_out = st.out(tfp, n);
-  if (!st.ok())
-    return 0;
-  if (fused2_enabled()) {
-    mifc::Fused2Params F = fused2_params(mifc::F2_TFP, nx, ny, d_tx, nullptr, d_xm, d_ym, nullptr, d_out, undef);
-    const int r = run_fused2(c, F, fdefined);
-    if (r == 0)
-      return 0;
-    if (r == 1)
-      return st.finish();
-  }
-  if (!tfp_two_passes(c, nx, ny, d_tx, d_xm, d_ym, d_out, fdefined, undef))
-    return 0;
-  return st.finish();
-}
-
-// plevelqvector's two scalars of a pressure level (:526-540, :564); false where the reference returns false
-static bool qvector_scales(float p, int compute, float* tscale, float* cscale)
-{
-  if (compute == 1 || compute == 3)
-    *tscale = 1.0f;
-  else if (compute == 2 || compute == 4)
-    *tscale = K_CP * powf(p / 1000.0f, 287.f / K_CP) / K_CP; // :539, host powf like the reference
-  else
-    return false;
-  *cscale = (float)((double)(-287.f) / ((double)p * 100.)); // :564
-  return true;
-}
-
-// The three passes of plevelqvector (:555-590) on device pointers, each ONE launch over the nlev levels: geostrophic wind x
-// and y into scratch batches, then the Q-vector component.  The flags thread through the passes like the reference's
-// fDefined: the x pass leaves NONE_DEFINED (:664), so the y pass always tests; the last pass tests whatever it is handed.
-// Its two scalars are tscale / cscale, or, with tscale_lev / cscale_lev (host, per level), tables that go to the device.
-static int qvector_three_passes(mifc_ctx* c, int nx, int ny, int nlev, const float* d_z, const float* d_t, const float* d_xm, const float* d_ym,
-                                const float* d_fc, int compute, float tscale, float cscale, const float* tscale_lev, const float* cscale_lev,
-                                float* d_out, int* fdefined, float undef)
-{
-  const size_t nb = (size_t)nx * ny * (size_t)nlev;
-  Staging st(c, MIFC_MEM_DEVICE);
-  float* d_ug = static_cast<float*>(st.scratch(nb * sizeof(float)));
-  float* d_vg = static_cast<float*>(st.scratch(nb * sizeof(float)));
-  if (!st.ok())
-    return 0;
-  const StencilCall pass1 = {mifc::ST_GWIND_X, nx, ny, nlev, d_z, nullptr, d_xm, d_ym, d_fc, d_ug, nullptr};
-  if (!run_stencil(c, pass1, fdefined, undef, MIFC_MEM_DEVICE))
-    return 0;
-  const StencilCall pass2 = {mifc::ST_GWIND_Y, nx, ny, nlev, d_z, nullptr, d_xm, d_ym, d_fc, d_vg, nullptr};
-  if (!run_stencil(c, pass2, fdefined, undef, MIFC_MEM_DEVICE))
-    return 0;
-  StencilCall pass3 = {compute < 3 ? mifc::ST_QVEC_X : mifc::ST_QVEC_Y, nx, ny, nlev, d_ug, d_vg, d_xm, d_ym, nullptr, d_out, nullptr};
-  pass3.f2 = d_t;
-  pass3.scale = tscale;
-  pass3.scale2 = cscale;
-  if (tscale_lev && cscale_lev) {
-    // the tables go up on the stream the passes run on; run_stencil() synchronises before it returns, so the host
-    // vectors outlive the copies
-    MIFC_HIP(c, hipMemcpyAsync(c->d_ab, tscale_lev, sizeof(float) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-    MIFC_HIP(c, hipMemcpyAsync(c->d_ab + c->cap_lev, cscale_lev, sizeof(float) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-    pass3.scale_lev = c->d_ab;
-    pass3.scale2_lev = c->d_ab + c->cap_lev;
-  }
-  return run_stencil(c, pass3, fdefined, undef, MIFC_MEM_DEVICE);
-}
-
-// plevelqvector, FieldCalculations.cc:505-595: geostrophic wind x and y into
-// the context's scratch, then the Q-vector component.  The flag threads through
-// the three passes like the reference's fDefined: the x pass leaves NONE_DEFINED
-// (:664), so the y pass always tests; the last pass tests whatever it is handed.
-int mifc_plevelqvector(mifc_ctx* c, int nx, int ny, const float* z, const float* t, const float* xmapr, const float* ymapr, const float* fcoriolis,
-                       float p, int compute, float* qcomp, int* fdefined, float undef, int memkind)
-{
-  CTX_OR_FAIL(c);
-  if (p <= 0.0 || nx < 3 || ny < 3) // :526-530
-    return 0;
-  float tscale, cscale;
-  if (!qvector_scales(p, compute, &tscale, &cscale))
-    return 0;
-  const size_t n = (size_t)nx * ny;
-  Staging st(c, memkind);
-  const float* d_z = st.in(z, n);
-  const float* d_t = st.in(t, n);
-  const float* d_xm = st.in(xmapr, n);
-  const float* d_ym = st.in(ymapr, n);
-  const float* d_fc = st.in(fcoriolis, n);
-  float* d_out = st.out(qcomp, n);
-  if (!st.ok())
-    return 0;
-  if (fused2_enabled()) {
-    mifc::Fused2Params F = fused2_params(compute < 3 ? mifc::F2_QVEC_X : mifc::F2_QVEC_Y, nx, ny, d_z, d_t, d_xm, d_ym, d_fc, d_out, undef);
-    F.scale = tscale;
-    F.scale2 = cscale;
-    const int r = run_fused2(c, F, fdefined);
-    if (r == 0)
-      return 0;
-    if (r == 1)
-      return st.finish();
-  }
-  if (!qvector_three_passes(c, nx, ny, 1, d_z, d_t, d_xm, d_ym, d_fc, compute, tscale, cscale, nullptr, nullptr, d_out, fdefined, undef))
-    return 0;
-  return st.finish();
-}
-
 // ----------------------------------------------------------------- batched
 
 int mifc_vortdiv_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* u, const float* v, const float* xmapr, const float* ymapr, float* rvort,
@@ -585,57 +395,15 @@ int mifc_stencil_levels(mifc_ctx* c, int op, int nx, int ny, int nlev, const flo
   return run_stencil(c, sc, fdefined, undef, memkind);
 }
 
-// ---- the f1 operators over a batch of levels (shared map factors) -----------------------------
-// advection runs on the batched stencil driver; thermalFrontParameter, plevelqvector and shapiro2_filter on
-// their one-launch kernels with grid.y = level, in two groups: the levels whose input flag is ALL_DEFINED
-// (no tests) and the others.  Grids those kernels do not take (nx % 4 != 0, unaligned) go level by level
-// through the single-field entry points.
-static int f1_levels_fallback(mifc_ctx* c, int op, int nx, int ny, int nlev, const float* f0, const float* f1, const float* xm, const float* ym,
-                              const float* fc, const float* level_p, int compute, float* out0, int* fdefined, float undef,
-                              const float* tscale = nullptr, const float* cscale = nullptr)
-{
-  const size_t n = (size_t)nx * ny;
-  if (op == MIFC_OP_TFP && nlev > 1) // widths the one-launch kernel does not take: the two passes, each over all levels
-    return tfp_two_passes(c, nx, ny, f0, xm, ym, out0, fdefined, undef, nlev);
-  if (op == MIFC_OP_QVECTOR && nlev > 1 && tscale && cscale) {
-    // the last pass takes its two scalars per level from device tables (they depend on the level's pressure)
-    if (!ensure_levels(c, (size_t)nlev))
-      return 0;
-    return qvector_three_passes(c, nx, ny, nlev, f0, f1, xm, ym, fc, compute, 0.f, 0.f, tscale, cscale, out0, fdefined, undef);
-  }
-  for (int l = 0; l < nlev; ++l) {
-    int rc;
-    if (op == MIFC_OP_TFP)
-      rc = mifc_thermalFrontParameter(c, nx, ny, f0 + l * n, xm, ym, out0 + l * n, fdefined + l, undef, MIFC_MEM_DEVICE);
-    else if (op == MIFC_OP_QVECTOR)
-      rc = mifc_plevelqvector(c, nx, ny, f0 + l * n, f1 + l * n, xm, ym, fc, level_p[l], compute, out0 + l * n, fdefined + l, undef, MIFC_MEM_DEVICE);
-    else
-      rc = mifc_shapiro2_filter(c, nx, ny, f0 + l * n, out0 + l * n, fdefined + l, undef, MIFC_MEM_DEVICE);
-    if (!rc)
-      return 0;
-  }
-  return 1;
-}
-
-// the end of both Shapiro batch routes: the result out of the scratch batch (in-place call), the outputs home, every flag
-// ALL_DEFINED
-static int shapiro_levels_finish(mifc_ctx* c, Staging& st, float* dout, const float* dst, size_t nb, int* fdefined, int nlev)
-{
-  if (dst != dout)
-    MIFC_HIP(c, hipMemcpyAsync(dout, dst, nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  if (!st.finish())
-    return 0;
-  for (int l = 0; l < nlev; ++l)
-    fdefined[l] = MIFC_ALL_DEFINED; // :2171
-  return 1;
-}
-
+// mifc_stencil_levels plus the rest of the stencil family over a batch of levels (shared map factors): advection runs on the
+// batched stencil driver here; thermalFrontParameter, plevelqvector and shapiro2_filter have their drivers in
+// mifc_capi_twostage.hip
 int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const float* f0, const float* f1, const float* f2, const float* xmapr,
                            const float* ymapr, const float* fcoriolis, const float* level_scalars, float scalar, int compute, float* out0,
                            float* out1, int* fdefined, float undef, int memkind)
 {
   CTX_OR_FAIL(c);
-  mifc::hostpipe_note_chunks(0, 0); // (the two-stage operators and the filter stage their batch whole and may not reach run_stencil)
+  mifc::hostpipe_note_chunks(0, 0); // (the two-stage operators and the filter stage their batch whole and may not reach run_stencil())
   if (op != MIFC_OP_ADVECTION && op != MIFC_OP_TFP && op != MIFC_OP_QVECTOR && op != MIFC_OP_SHAPIRO2)
     return mifc_stencil_levels(c, op, nx, ny, nlev, f0, f1, xmapr, ymapr, fcoriolis, out0, out1, fdefined, undef, memkind);
   if (nx < 3 || ny < 3 || nlev < 1 || !f0 || !out0 || !fdefined)
@@ -648,134 +416,7 @@ int mifc_stencil_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const 
     sc.scale = (float)(-3600. * (double)scalar); // :1963
     return run_stencil(c, sc, fdefined, undef, memkind);
   }
-  const size_t n = (size_t)nx * ny, nb = n * (size_t)nlev;
-  std::vector<float> tscale, cscale;
-  if (op == MIFC_OP_QVECTOR) { // :526-540, per level like the single-field call
-    if (!f1 || !fcoriolis || !level_scalars)
-      return 0;
-    tscale.resize(nlev);
-    cscale.resize(nlev);
-    for (int l = 0; l < nlev; ++l) {
-      if (level_scalars[l] <= 0.0 || !qvector_scales(level_scalars[l], compute, &tscale[l], &cscale[l]))
-        return 0;
-    }
-  }
-  Staging st(c, memkind);
-  const float* d0 = st.in(f0, nb);
-  const float* d1 = (op == MIFC_OP_QVECTOR) ? st.in(f1, nb) : nullptr;
-  const float* dxm = (op != MIFC_OP_SHAPIRO2) ? st.in(xmapr, n) : nullptr;
-  const float* dym = (op != MIFC_OP_SHAPIRO2) ? st.in(ymapr, n) : nullptr;
-  const float* dfc = (op == MIFC_OP_QVECTOR) ? st.in(fcoriolis, n) : nullptr;
-  float* dout = st.out(out0, nb);
-  if (!st.ok() || !ensure_levels(c, (size_t)nlev))
-    return 0;
-  if (op != MIFC_OP_SHAPIRO2 && (!dxm || !dym))
-    return 0;
-  // the levels in two groups: ALL_DEFINED input first
-  std::vector<int> order;
-  order.reserve(nlev);
-  for (int l = 0; l < nlev; ++l)
-    if (fdefined[l] == MIFC_ALL_DEFINED)
-      order.push_back(l);
-  const int n_all = (int)order.size();
-  for (int l = 0; l < nlev; ++l)
-    if (fdefined[l] != MIFC_ALL_DEFINED)
-      order.push_back(l);
-  bool fused = nlev <= 65535;
-  if (op == MIFC_OP_SHAPIRO2) {
-    float* dst = dout;
-    if (dout == d0) { // in place (allowed by the reference, :2088): through a scratch batch
-      dst = static_cast<float*>(st.scratch(nb * sizeof(float)));
-      if (!st.ok())
-        return 0;
-    }
-    fused = fused && mifc::env().shapiro_fused && mifc::shapiro2_fused_supported(nx, ny, d0, dst) && (n % 4 == 0 || mifc::env().shapiro_regs);
-    if (fused) {
-      MIFC_HIP(c, hipMemcpyAsync(c->d_levels, order.data(), sizeof(int) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-      if (n_all > 0)
-        MIFC_LAUNCH(c, mifc::launch_shapiro2_fused_levels(nx, ny, 1, undef, d0, dst, n_all, (long)n, c->d_levels, c->stream));
-      if (nlev - n_all > 0)
-        MIFC_LAUNCH(c, mifc::launch_shapiro2_fused_levels(nx, ny, 0, undef, d0, dst, nlev - n_all, (long)n, c->d_levels + n_all, c->stream));
-      return shapiro_levels_finish(c, st, dout, dst, nb, fdefined, nlev);
-    }
-    // widths the one-launch kernel does not take: the sweep-by-sweep path over the levels of each flag group (five launches
-    // per group whatever the number of levels), in place on the output batch like the reference (:2099-2104)
-    if (nlev > 1 && nlev <= 65535 && n <= 0x7fffffffu) {
-      const bool any_tested = n_all < nlev;
-      float* sweep = static_cast<float*>(st.scratch(nb * sizeof(float)));
-      unsigned char* masks = any_tested ? static_cast<unsigned char*>(st.scratch(2 * nb)) : nullptr;
-      if (!st.ok())
-        return 0;
-      if (dst != d0)
-        MIFC_HIP(c, hipMemcpyAsync(dst, d0, nb * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      MIFC_HIP(c, hipMemcpyAsync(c->d_levels, order.data(), sizeof(int) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-      mifc::ShapiroParams SP;
-      SP.nx = nx;
-      SP.ny = ny;
-      SP.undef = undef;
-      SP.f1 = dst;
-      SP.f2 = sweep;
-      SP.mask_x = masks;
-      SP.mask_y = any_tested ? masks + nb : nullptr;
-      if (n_all > 0) {
-        SP.all_defined = 1;
-        MIFC_LAUNCH(c, mifc::launch_shapiro2_levels(SP, n_all, c->d_levels, c->stream));
-      }
-      if (any_tested) {
-        SP.all_defined = 0;
-        MIFC_LAUNCH(c, mifc::launch_shapiro2_levels(SP, nlev - n_all, c->d_levels + n_all, c->stream));
-      }
-      return shapiro_levels_finish(c, st, dout, dst, nb, fdefined, nlev);
-    }
-  } else {
-    mifc::Fused2Params F = fused2_params((op == MIFC_OP_TFP) ? mifc::F2_TFP : (compute < 3 ? mifc::F2_QVEC_X : mifc::F2_QVEC_Y), nx, ny, d0, d1, dxm,
-                                         dym, dfc, dout, undef);
-    F.counts = c->d_counts;
-    F.level_stride = (long)n;
-    fused = fused && fused2_enabled() && mifc::fused2_supported(F) && 3 * (size_t)nlev <= 5 * c->cap_lev;
-    if (fused) {
-      if (!pinned_acquire(c))
-        return 0;
-      MIFC_HIP(c, hipMemcpyAsync(c->d_levels, order.data(), sizeof(int) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-      if (op == MIFC_OP_QVECTOR) {
-        MIFC_HIP(c, hipMemcpyAsync(c->d_ab, tscale.data(), sizeof(float) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-        MIFC_HIP(c, hipMemcpyAsync(c->d_ab + c->cap_lev, cscale.data(), sizeof(float) * (size_t)nlev, hipMemcpyHostToDevice, c->stream));
-        F.scale_lev = c->d_ab;
-        F.scale2_lev = c->d_ab + c->cap_lev;
-      }
-      MIFC_HIP(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(u64) * (size_t)nlev, c->stream));
-      for (int group = 0; group < 2; ++group) {
-        const int first = group == 0 ? 0 : n_all, count = group == 0 ? n_all : nlev - n_all;
-        if (count == 0)
-          continue;
-        F.check = group;
-        F.n_launch_levels = count;
-        F.levels = c->d_levels + first;
-        MIFC_LAUNCH(c, mifc::launch_fused2(F, c->stream));
-      }
-      MIFC_HIP(c, hipMemcpyAsync(pinned_counts(c), c->d_counts, 3 * sizeof(u64) * (size_t)nlev, hipMemcpyDeviceToHost, c->stream));
-      MIFC_HIP(c, hipStreamSynchronize(c->stream));
-      const u64* cnt = pinned_counts(c);
-      std::vector<int> redo;
-      for (int l = 0; l < nlev; ++l) {
-        const u64* k = cnt + 3 * (size_t)l;
-        // thermalFrontParameter: the second pass is tested only if the first left something undefined (:2286); see run_fused2()
-        if (op == MIFC_OP_TFP && fdefined[l] != MIFC_ALL_DEFINED && k[0] == 0 && k[2] != 0)
-          redo.push_back(l);
-        else
-          fdefined[l] = mifc_classify(k[1], (u64)n - 2 * (u64)nx); // :2303, :590
-      }
-      for (int l : redo) // rare: those levels again, pass by pass
-        if (!tfp_two_passes(c, nx, ny, d0 + (size_t)l * n, dxm, dym, dout + (size_t)l * n, fdefined + l, undef))
-          return 0;
-      return st.finish();
-    }
-  }
-  // level by level on the staged (device) batch
-  if (!f1_levels_fallback(c, op, nx, ny, nlev, d0, d1, dxm, dym, dfc, level_scalars, compute, dout, fdefined, undef,
-                          tscale.empty() ? nullptr : tscale.data(), cscale.empty() ? nullptr : cscale.data()))
-    return 0;
-  return st.finish();
+  return two_stage_levels_ex(c, op, nx, ny, nlev, f0, f1, xmapr, ymapr, fcoriolis, level_scalars, compute, out0, fdefined, undef, memkind);
 }
 
 int mifc_vortdiv_levels_enqueue(mifc_ctx* c, int nx, int ny, int nlev, const float* u, const float* v, const float* xmapr, const float* ymapr,

@@ -139,10 +139,9 @@ float* pinned_ab(mifc_ctx* c);
 
 // The device homes of one call's host fields.  Every staged field and every scratch block takes the
 // context's next slot (each slot an allocation of its own that only grows); the destructor hands the
-// slots back.  So a driver or an entry point called while a caller's Staging is alive continues after
-// the caller's slots (the level-by-level fallback of mifc_stencil_levels_ex calls entry points with the
-// batch staged, which is why enter() does not start the slots again), and calls one after the other use
-// the same ones.  A pointer handed out is good until the object goes.  A null pointer, MIFC_MEM_DEVICE
+// slots back.  So a driver called while a caller's Staging is alive continues after the caller's slots
+// (the passes of the two-stage operators go through run_stencil() with the batch staged), and calls one
+// after the other use the same ones.  A pointer handed out is good until the object goes.  A null pointer, MIFC_MEM_DEVICE
 // memory and a host field held by mifc_hold_field pass through and take no slot.
 class Staging
 {

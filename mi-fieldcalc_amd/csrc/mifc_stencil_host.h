@@ -1,5 +1,6 @@
 // mifc_stencil_host.h -- the host-side description of a stencil request, shared by the stencil boundary
-// (mifc_capi_stencil.hip, which implements what is declared here) and the row-slab plan (mifc_slab.hip).  Not installed.
+// (mifc_capi_stencil.hip, which implements what is declared here unless noted), the two-stage operators and the Shapiro
+// filter (mifc_capi_twostage.hip) and the row-slab plan (mifc_slab.hip).  Not installed.
 #ifndef MIFC_STENCIL_HOST_H
 #define MIFC_STENCIL_HOST_H
 
@@ -34,6 +35,15 @@ mifc::StencilParams stencil_params(const StencilCall& sc, float undef);
 // One tested level of a big field through the one-shot stencil kernels: room for their workgroups' counts
 // (StencilParams::partials) in the context's buffer.
 void stencil_partials(mifc_ctx* c, mifc::StencilParams& P);
+
+// The synchronous stencil driver, single field or level batch: stages the request's fields (memkind), launches, reads the
+// counts back and classifies.  fdefined[nlev]: the input flags, then the output flags.  Notes its kernel form.
+int run_stencil(mifc_ctx* c, const StencilCall& sc, int* fdefined, float undef, int memkind);
+
+// mifc_capi_twostage.hip: the MIFC_OP_TFP, MIFC_OP_QVECTOR and MIFC_OP_SHAPIRO2 branches of mifc_stencil_levels_ex, after its
+// checks of nx, ny, nlev, f0, out0 and fdefined
+int two_stage_levels_ex(mifc_ctx* c, int op, int nx, int ny, int nlev, const float* f0, const float* f1, const float* xmapr, const float* ymapr,
+                        const float* fcoriolis, const float* level_scalars, int compute, float* out0, int* fdefined, float undef, int memkind);
 
 } // namespace mifc_host
 

@@ -1380,7 +1380,8 @@ def test_stencil_levels_ex_f1_operators(gpu_ctx, oracle, nx, ny, nlev, device):
     """mifc_stencil_levels_ex: advection, thermalFrontParameter, plevelqvector (pressure per level) and
     shapiro2_filter over a batch == the per-level reference call, flags included.  Mixed input flags in
     one batch (the two-stage kernels run the ALL_DEFINED levels and the tested ones as separate launches),
-    a level whose flag lies, and a width the one-launch kernels do not take (129: level-by-level path)."""
+    a level whose flag lies, and ragged widths (129, 949), which the one-launch kernels take like the others: every
+    case here runs on them (fused2, shapiro_fused).  tests/test_gpu_two_stage_seams.py has the widths they refuse."""
     import torch
 
     import mi_fieldcalc_amd.synth as synth
@@ -1405,8 +1406,10 @@ def test_stencil_levels_ex_f1_operators(gpu_ctx, oracle, nx, ny, nlev, device):
     host = (lambda a: a.cpu().numpy()) if device else (lambda a: a)
     dxm, dym, dfc = dev(xm), dev(ym), dev(fcor)
 
-    def check(name, res, per_level):
+    def check(name, res, per_level, form=None):
         assert res is not None, name
+        if form:
+            gpu_util.check_form(gpu_ctx, form, what=name)
         out, fo = res
         out = host(out)
         for l in range(nlev):
@@ -1417,12 +1420,12 @@ def test_stencil_levels_ex_f1_operators(gpu_ctx, oracle, nx, ny, nlev, device):
     check("advection", gpu_ctx.stencil_levels_ex("advection", dev(z), dev(u), dev(v), dxm, dym, scalar=1.0 / 3600.0, fdefined=flags),
           lambda l: oracle.call("advection", nx, ny, z[l], u[l], v[l], xm, ym, 1.0 / 3600.0, fdefined=int(flags[l])))
     check("tfp", gpu_ctx.stencil_levels_ex("thermalFrontParameter", dev(z), xmapr=dxm, ymapr=dym, fdefined=flags),
-          lambda l: oracle.call("thermalFrontParameter", nx, ny, z[l], xm, ym, fdefined=int(flags[l])))
+          lambda l: oracle.call("thermalFrontParameter", nx, ny, z[l], xm, ym, fdefined=int(flags[l])), form="fused2")
     for c in (1, 2, 3, 4):
         check("qvector%d" % c, gpu_ctx.stencil_levels_ex("plevelqvector", dev(z), dev(t), None, dxm, dym, dfc, level_scalars=pres, compute=c, fdefined=flags),
-              lambda l: oracle.call("plevelqvector", nx, ny, z[l], t[l], xm, ym, fcor, float(pres[l]), c, fdefined=int(flags[l])))
+              lambda l: oracle.call("plevelqvector", nx, ny, z[l], t[l], xm, ym, fcor, float(pres[l]), c, fdefined=int(flags[l])), form="fused2")
     check("shapiro", gpu_ctx.stencil_levels_ex("shapiro2_filter", dev(z), fdefined=flags),
-          lambda l: oracle.call("shapiro2_filter", nx, ny, z[l], fdefined=int(flags[l])))
+          lambda l: oracle.call("shapiro2_filter", nx, ny, z[l], fdefined=int(flags[l])), form="shapiro_fused")
     # invalid arguments -> false, like the per-level calls
     assert gpu_ctx.stencil_levels_ex("plevelqvector", dev(z), dev(t), None, dxm, dym, dfc, level_scalars=-pres, compute=1, fdefined=flags) is None
     assert gpu_ctx.stencil_levels_ex("plevelqvector", dev(z), dev(t), None, dxm, dym, dfc, level_scalars=pres, compute=7, fdefined=flags) is None
