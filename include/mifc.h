@@ -524,6 +524,68 @@ int mifc_vderiv_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
                        const float* levels /* HOST float[nlev] */, int method, float* const* fres, int* fdefined_out,
                        float* const* fmag, int* fdefined_mag, float undef, int memkind);
 
+/* ---- EXTENSION: running vertical integrals of level batches --------------------------------------------------
+ * Not a miutil::fieldcalc function: the height of hybrid levels (the hydrostatic integration of virtual temperature over
+ * ln p from the surface upward), the mass above or below every level, the optical depth or cloud water path down to each
+ * level, the running precipitable water, the thickness between pressure levels -- any integral of x dc whose upper limit
+ * is every level in turn; the reference leaves them to a host loop of its caller.  nfields fields of [nlev][ny][nx] and
+ * one coordinate per level go in -- the three coordinate forms of mifc_vderiv_* above --, fres[f] is [nlev][ny][nx]: the
+ * integral up to each input level, itself a level batch (a height batch for mifc_vinterp_fields, say).  Per cell i and
+ * field f:
+ *   1. Coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it (hybrid: the float product, then the float sum);
+ *      mifc_vcumul_levels: c_k = levels[k].  A coordinate is usable when it is defined by that rule, is not NaN and, with
+ *      MIFC_VCUMUL_LOG, is > 0.  g(c) = (double)c for MIFC_VCUMUL_LINEAR = 0, log((double)c) for MIFC_VCUMUL_LOG = 1.
+ *   2. Walk order.  k(0), k(1), ... is 0, 1, ..., nlev - 1 for MIFC_VCUMUL_FROM_FIRST = 0 and nlev - 1, ..., 0 for
+ *      MIFC_VCUMUL_FROM_LAST = 1.  No monotonicity is assumed; the integral is signed.
+ *   3. Point.  Point m is usable for f when c_m is usable and x_m passes is_defined(fdefined_in[f * nlev + m] ==
+ *      ALL_DEFINED, x_m, undef).
+ *   4. Start.  S = +0.0.  If `start` is given it must be usable in the sense of rule 1 under fdef_start; otherwise every
+ *      level of every field is undef at i.  If it is given and point k(0) is usable, S = x_{k(0)} * (g(c_{k(0)}) -
+ *      g(start_i)): the integrand is held constant between the start and the first level.
+ *   5. Step.  With a = k(m), b = k(m + 1): S += ((x_a + x_b) * 0.5) * (g(c_b) - g(c_a)), all in double, every operation
+ *      rounded on its own (no contraction): the operation order of rule 5 of mifc_vlayer_*.
+ *   6. Holes.  An integral with a hole in it is a wrong number, not a partial one: from the first point in walk order that
+ *      is not usable for f, that level and every later one are undef for f; earlier levels are unaffected.  A base[f]
+ *      that fails is_defined(fdef_base[f] == ALL_DEFINED, base_f[i], undef) or is NaN makes every level of f undef at i.
+ *   7. Result.  (float)((double)base_f[i] + scale_f * S) at each level: the product rounded, then the sum; without a
+ *      base the sum is absent.  A computed NaN or infinity is a value: not undef, not counted.
+ *   8. Flags.  fdefined_out[f * nlev + k] = checkDefined(cells left undef at level k, nx * ny).
+ * MIFC_VCUMUL_LINEAR is bit for bit this definition (restated in numpy in tests/vcumul_restate.py).  MIFC_VCUMUL_LOG
+ * depends on the device's double log(): a result is the definition's float or its neighbour, as for MIFC_VINTERP_LOG;
+ * undef cells and flags are exact.  In the `levels` form g(levels[k]) is computed once per level on the host.  The
+ * logarithm is paid once per cell and level however many fields the call carries.
+ * Arguments as for mifc_vderiv_*: `fields`, `fres` HOST arrays of nfields pointers (1..8); `fdefined_in`,
+ * `fdefined_out` HOST int[nfields * nlev], field-major; `alevel`, `blevel`, `levels` HOST float[nlev]; `fdef_coord`
+ * HOST int[nlev] or NULL.  `start` is optional: [ny][nx] of the call's memory kind, the coordinate at which the integral
+ * begins (ps); NULL: it begins at the first walked level.  `base` is optional: a HOST array of nfields pointers to
+ * [ny][nx] (the table or any entry may be NULL), the value added to the result (the surface height); `fdef_base` HOST
+ * int[nfields] or NULL = SOME_DEFINED.  `scale` is optional: HOST double[nfields], NULL = 1.0 (-Rd / g, 1 / g).
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; nfields outside
+ * 1..8; a negative nx or ny; an unknown method or from; a null pointer that is required; a NaN scale[f]; hybrid form: a
+ * level whose (alevel, blevel) the reference's bad_hlevel (FieldCalculations.cc:298) rejects; `levels` form: a NaN
+ * level, or MIFC_VCUMUL_LOG with a level <= 0; an output that overlaps an input, the coordinate, ps, start, a base plane
+ * or another output by byte range (in-place is not offered); a call made while a mifc_graph capture is open.  Zero
+ * cells: the flags are ALL_DEFINED, the call returns 1.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time,
+ * MIFC_VCUMUL_CHUNK_MIB of device memory (default 256).  Every input level is read once and every output level written
+ * once per call.  mifc_last_vcumul_form: a diagnostic for tests, the calling thread's last call that
+ * launched: "v=4 fields=4 method=log from=last launches=2" -- cells per lane, fields of the first pass, launches in all. */
+enum { MIFC_VCUMUL_LINEAR = 0, MIFC_VCUMUL_LOG = 1 };
+enum { MIFC_VCUMUL_FROM_FIRST = 0, MIFC_VCUMUL_FROM_LAST = 1 };
+int mifc_vcumul_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* ps, int fdef_ps, const float* alevel, const float* blevel, int method, int from,
+                        const float* start, int fdef_start, const float* const* base, const int* fdef_base, const double* scale,
+                        float* const* fres, int* fdefined_out, float undef, int memkind);
+int mifc_vcumul_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, int method, int from,
+                       const float* start, int fdef_start, const float* const* base, const int* fdef_base, const double* scale,
+                       float* const* fres, int* fdefined_out, float undef, int memkind);
+int mifc_vcumul_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                       const float* levels /* HOST float[nlev] */, int method, int from, const float* start, int fdef_start,
+                       const float* const* base, const int* fdef_base, const double* scale, float* const* fres,
+                       int* fdefined_out, float undef, int memkind);
+const char* mifc_last_vcumul_form(void);
+
 /* ---- EXTENSION: level batches sampled at arbitrary points (regridding, cross-sections, soundings) ------------
  * Not a miutil::fieldcalc function: the reference's callers take a field to a flight route, a section line, a list of
  * stations or the grid of another projection on the host, level by level (their field class has an

@@ -133,6 +133,11 @@ SIGNATURES = {
     "mifc_vderiv_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
     "mifc_vderiv_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "p", "pi", "p", "pi", "f", "i"]),
     "mifc_vderiv_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "pi", "p", "pi", "f", "i"]),
+    # EXTENSION: running vertical integrals of level batches (base: a host table of pointers or None, scale: host double array or None)
+    "mifc_vcumul_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
+    "mifc_vcumul_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
+    "mifc_vcumul_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
+    "mifc_last_vcumul_form": ("s", []),
     # EXTENSION: level batches sampled at arbitrary points (fields, fres: host tables of pointers; xpos, ypos: where the fields are)
     "mifc_hinterp_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_last_hinterp_form": ("s", []),

@@ -12,6 +12,11 @@ ENS_SUM, ENS_MEAN, ENS_STDDEV, ENS_EXTREME, ENS_PROBABILITY = 0, 1, 2, 3, 4
 VLAYER_PRODUCTS = {"integral": 1, "mean": 2, "max": 3, "min": 4, "coord_of_max": 5, "coord_of_min": 6}
 # the methods of mifc_vderiv_* (MIFC_VDERIV_*)
 VDERIV_METHODS = {"centred": 0, "weighted": 1}
+# the methods and walk directions of mifc_vcumul_* (MIFC_VCUMUL_*)
+VCUMUL_METHODS = {"linear": 0, "log": 1}
+VCUMUL_FROM = {"first": 0, "last": 1}
+# miutil::constants r and g (MetConstants.h): the gas constant of dry air, J / (kg K), and gravity, m / s^2
+R_DRY, GRAVITY = 287.0, 9.8
 # the methods of mifc_hinterp_levels (MIFC_HINTERP_*)
 HINTERP_METHODS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 # the modes and product groups of mifc_hstats_levels (MIFC_HSTATS_*)

@@ -55,6 +55,7 @@ void env_reload()
   e.vinterp_chunk_mib = positive_int("MIFC_VINTERP_CHUNK_MIB");
   e.vlayer_chunk_mib = positive_int("MIFC_VLAYER_CHUNK_MIB");
   e.vderiv_chunk_mib = positive_int("MIFC_VDERIV_CHUNK_MIB");
+  e.vcumul_chunk_mib = positive_int("MIFC_VCUMUL_CHUNK_MIB");
   e.hinterp_chunk_mib = positive_int("MIFC_HINTERP_CHUNK_MIB");
   e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
   e.hinterp_level_chunk = positive_int("MIFC_HINTERP_LEVEL_CHUNK");

@@ -426,6 +426,46 @@ struct VderivParams
 };
 hipError_t launch_vderiv(const VderivParams& prm, hipStream_t stream);
 
+// ------------------------------------ running vertical integrals of level batches (mifc_vcumul.hip), EXTENSION
+// One launch walks the `nlev` levels of `n` columns once, from level 0 upward in index (from = 0) or from level nlev - 1
+// downward (from = 1), for up to VCUMUL_PASS fields and stores, per field and level, the trapezoid integral of the field
+// over the coordinate (method 0) or over its logarithm (method 1) from the start of the walk to that level:
+// out[f] + k * out_stride.  The host launches again for the fields beyond VCUMUL_PASS.  Inputs, `coord`, `ab`, `lev_bits`
+// (bit f0 + f = field f of the launch is flagged ALL_DEFINED at level k, bit VINTERP_COORD_BIT = the coordinate is), vec4
+// and kind (VDERIV_HYBRID / _FIELD / _LEVELS) as in VderivParams.  kind VDERIV_LEVELS: lev_g[k] = g(levels[k]), from the
+// host.  start: n floats or null (start_all: flagged ALL_DEFINED); base[f]: n floats or null (bit f of base_all: flagged
+// ALL_DEFINED); scale[f]: the factor of the sum.  Counters: n_undefined[(f0 + f) * nlev + k], zeroed by the caller; a
+// workgroup gathers its counts in VCUMUL_PASS * nlev words of dynamic LDS when lds_counts is set (the launcher sets it
+// where that fits), otherwise a wave adds to the global counters itself.
+const int VCUMUL_MAX_FIELDS = 8, VCUMUL_PASS = 4;
+struct VcumulParams
+{
+  int kind;    // VDERIV_HYBRID / VDERIV_FIELD / VDERIV_LEVELS
+  int method;  // MIFC_VCUMUL_LINEAR / MIFC_VCUMUL_LOG
+  int from;    // MIFC_VCUMUL_FROM_FIRST / MIFC_VCUMUL_FROM_LAST
+  int nfields; // of this launch, 1 .. VCUMUL_PASS
+  int f0;      // the call's field of the launch's field 0 (level bits, counters)
+  int n;       // columns of this launch
+  int nlev;    // >= 2
+  int vec4;
+  int ps_all;  // hybrid: fdef_ps == ALL_DEFINED
+  int start_all, base_all;
+  int lds_counts; // set by launch_vcumul
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[VCUMUL_PASS];
+  float* out[VCUMUL_PASS];
+  const float* base[VCUMUL_PASS];
+  double scale[VCUMUL_PASS];
+  const float* coord;
+  const float* start;
+  const float* ab;
+  const unsigned int* lev_bits;
+  const double* lev_g;
+  u64* n_undefined;
+};
+hipError_t launch_vcumul(const VcumulParams& prm, hipStream_t stream);
+
 // ------------------------------------ level batches sampled at arbitrary points (mifc_hinterp.hip), EXTENSION
 // One launch samples `nlev` levels of up to hinterp_pass_fields(method) fields at `npos` points: a gather.  A lane owns
 // one point, a workgroup 256 consecutive points and the levels [blockIdx.y * chunk, + chunk) of the launch; level k of

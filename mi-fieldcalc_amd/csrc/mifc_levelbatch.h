@@ -1,5 +1,5 @@
 // mifc_levelbatch.h -- the host driver of the entries that walk level batches column by column (mifc_capi_vinterp.hip,
-// mifc_capi_vlayer.hip, mifc_capi_vderiv.hip; the head, the refusals and the level table also serve
+// mifc_capi_vlayer.hip, mifc_capi_vderiv.hip, mifc_capi_vcumul.hip; the head, the refusals and the level table also serve
 // mifc_capi_hinterp.hip, which samples the levels instead of walking them): the head of such a call and the refusals
 // that read only it, the overlap rule, the device table of the per-level scalars, and where the planes of the call are on the device --
 // the caller's own for device memory, a band of rows at a time for host memory (columns are independent, so a band of
@@ -153,13 +153,13 @@ private:
     g_[n_] = {planes ? host : nullptr, nullptr, host ? planes : 0, out};
     return &g_[n_++];
   }
-  static const int MAX_GROUPS = 24; // 8 fields, the coordinate, two bounds, 8 + 4 outputs
+  static const int MAX_GROUPS = 28; // 8 fields, the coordinate, two bounds, 8 + 4 outputs; or a start, 8 bases and 8 outputs
   PlaneGroup g_[MAX_GROUPS];
   int n_ = 0;
   size_t rows_ = 0;
 };
 
-// What VinterpParams, VlayerParams and VderivParams have alike, everything else zero.
+// What VinterpParams, VlayerParams, VderivParams and VcumulParams have alike, everything else zero.
 template <class Params>
 void fill_params(Params& P, const LevelBatchCall& a, const LevelTable& tab, const BandPlan& plan, const PlaneGroup* coord)
 {
