@@ -586,6 +586,87 @@ int mifc_vcumul_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
                        int* fdefined_out, float undef, int memkind);
 const char* mifc_last_vcumul_form(void);
 
+/* ---- EXTENSION: parcel ascent over level batches: CAPE, CIN, LCL, LFC, EL -------------------------------------
+ * Not a miutil::fieldcalc function.  The reference lifts a parcel across ONE layer, in showalterIndex
+ * (FieldCalculations.cc:872): along the dry adiabat to the upper level, then humidity and heat adjusted there in seven
+ * iterations.  Stepping that adjustment from level to level through a batch gives the parcel curve; one more walk of the
+ * column gives the convective available potential energy, the inhibition and the three levels a forecaster reads off a
+ * sounding.  t is [nlev][ny][nx] in K, pressure in hPa in one of the three coordinate forms of mifc_vcumul_*.  The
+ * parcel's source is a level of the batch (src_level >= 0: that level's t and pressure, with the specific humidity q_src
+ * [ny][nx] in kg/kg) or three planes (src_level == -1: t_src, q_src, p_src -- a mixed-layer parcel from mifc_vlayer_*
+ * means).  Outputs, each optional, at least one: the planes cape (J/kg), cin (J/kg, <= 0), plcl, plfc, pel (hPa) and the
+ * batch tparcel [nlev][ny][nx], the parcel temperature at every walked level.  Constants as MetConstants.h: cp = 1004,
+ * Rd = 287, eps = 0.622, xlh = 2.501e6, t0 = 273.15, kappa = Rd / cp, all float.  Per cell:
+ *   1. Walk and usable points.  Walk order k(0), k(1), ... as rule 2 of mifc_vcumul_* (from = MIFC_VPARCEL_FROM_FIRST /
+ *      _LAST).  p_k exactly as rule 1 of mifc_vinterp_* gives it (hybrid: the float product, then the float sum;
+ *      mifc_vparcel_levels: levels[k]).  A point is usable when p_k is defined by that rule, is not NaN, is > 0 and is
+ *      strictly below the pressure of the previous point of the walk (the source first), and t_k passes
+ *      is_defined(fdefined_in[k] == ALL_DEFINED, t_k, undef) and is not NaN.  With a source level the walk is the positions
+ *      behind that level; levels in front of it are not walked.  With source planes the positions in walk order are
+ *      skipped until the first whose pressure is < p_src (an undefined pressure is not); it is the first walked point.
+ *      The first walked point that is not usable ends the walk: tparcel is undef from there on and every plane is undef
+ *      at the cell -- an integral with a hole is a wrong number (rule 6 of mifc_vcumul_*).  The source is usable when its
+ *      temperature, humidity and pressure are defined under their flags (the level's flag, fdef_tsrc, fdef_qsrc,
+ *      fdef_psrc, the pressure form's rule), none is NaN, the pressure is > 0 and the temperature (cp * T) / cp lies in
+ *      the saturation table (MetConstants.h:64-80); otherwise everything is undef at the cell.
+ *   2. State.  tcl = cp * T_src and qcl = q_src, both float.  pi(p) = cp * powf(p * p0inv, kappa), the reference's
+ *      pi_from_p, float.  The parcel temperature at any point is tcl / cp (float); at a source level tparcel holds it too.
+ *   3. Step from point a to the next point b.  Dry: tcl = tcl * (pi_b / pi_a), the float quotient rounded first, then the
+ *      float product.  Saturation test: x = tcl / cp - t0 looked up as showalterIndex does (:949-953), qsat = eps * esat /
+ *      p_b in float (the product, then the quotient).  A temperature outside the table here ends the walk as in rule 1.
+ *      If qcl > qsat the seven trips of :948-960 run verbatim with p500 := p_b, its `break` outside the table and its a1
+ *      from qcl included; otherwise the state is unchanged.  tparcel_b = tcl / cp.  The deficit of the point is
+ *      d_b = (double)qsat - (double)qcl with the values of the test (before the trips); at the source d = qsat_src - q_src.
+ *   4. Buoyancy.  B_b = (double)tparcel_b - (double)t_b; at the source B = +0.  Between two points B is linear in
+ *      ln p, l = log((double)p).  There is NO virtual-temperature correction: humidity does not enter B.
+ *   5. LCL.  The source if q_src >= qsat_src: plcl = p_src.  Otherwise at the first point b with qcl > qsat, a the point
+ *      before it: w = d_a / (d_a - d_b), l_lcl = l_a + w * (l_b - l_a), B_lcl = B_a + w * (B_b - B_a), plcl =
+ *      (float)exp(l_lcl).  The LCL cuts the piece (a, b) of B into (a, LCL) and (LCL, b).  Never saturated: plcl, plfc,
+ *      pel, cin undef, cape = +0.
+ *   6. Pieces, in walk order.  For a piece from (Ba, la) to (Bb, lb), h = la - lb: `up` is !(Ba > 0) and Bb > 0, `down`
+ *      is Ba > 0 and !(Bb > 0).  With up or down: w0 = Ba / (Ba - Bb), lx = la + w0 * (lb - la), h1 = w0 * h, h2 = h - h1,
+ *      A1 = (Ba * 0.5) * h1, A2 = (Bb * 0.5) * h2; pos = A2, neg = A1 for up and pos = A1, neg = A2 for down.  Otherwise
+ *      A = ((Ba + Bb) * 0.5) * h is pos where both are > 0, else neg.  While no LFC is known: cin_sum += neg; if the piece
+ *      lies at or above the LCL and is `up`, the LFC is its zero, plfc = (float)exp(lx), and cape_sum += pos.  Once the
+ *      LFC is known: cape_sum += pos, and a `down` piece sets pel = (float)exp(lx) (the highest one stays).  The LFC is the
+ *      LCL itself when B_lcl > 0 (settled between the two pieces of rule 5).  No LFC: plfc, pel, cin undef, cape = +0.
+ *   7. EL.  pel is undef if no piece went down behind the LFC or if B > 0 at the last walked point; CAPE then ends there.
+ *   8. Integrals.  cape = (float)(287.0 * cape_sum), cin = (float)(287.0 * cin_sum); the sums start at +0.0; everything
+ *      in rules 4 to 8 is double, every operation rounded on its own (no contraction), in the order written here and in
+ *      tests/vparcel_restate.py.
+ *   9. Flags.  fdefined_out[0..4] = checkDefined(cells left undef, nx * ny) of cape, cin, plcl, plfc, pel,
+ *      fdefined_out[5 + k] of tparcel's level k; the entries of outputs that are not asked for are not written.
+ * tests/vparcel_restate.py is this definition in numpy.  Undef cells and flags are exact.  Values depend on the device's
+ * x^kappa (the correctly rounded float or its neighbour) and on its double log / exp: they lie within the response of the
+ * definition to a one-ulp change of pi (tests/test_gpu_vparcel.py); a cell's bits do not depend on the cells per lane,
+ * the launch shape, the memory kind or the banding.  In the `levels` form pi of every level is computed once on the host.
+ * Arguments: t, ps / p, t_src, q_src, p_src and the outputs in the call's memory kind; fdefined_in HOST int[nlev] or NULL
+ * = SOME_DEFINED; alevel, blevel, levels HOST float[nlev]; fdef_coord HOST int[nlev] or NULL; fdefined_out HOST
+ * int[5 + nlev].  t_src and p_src are not read with a source level and may be NULL then.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; a negative nx or
+ * ny; an unknown from; src_level outside -1..nlev - 1; a null pointer that is required; no output at all; hybrid form: a
+ * level whose (alevel, blevel) the reference's bad_hlevel (FieldCalculations.cc:298) rejects; `levels` form: a NaN level
+ * or a level <= 0; an output that overlaps an input, the pressure, ps, a source plane or another output by byte range; a
+ * call made while a mifc_graph capture is open.  Zero cells: the flags are ALL_DEFINED, the call returns 1.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time,
+ * MIFC_VPARCEL_CHUNK_MIB of device memory (default 256).  Every input level is read once per call.
+ * mifc_last_vparcel_form: a diagnostic for tests, the calling thread's last call that launched:
+ * "v=4 form=hlevels from=last src=136 outputs=6 launches=1". */
+enum { MIFC_VPARCEL_FROM_FIRST = 0, MIFC_VPARCEL_FROM_LAST = 1 };
+int mifc_vparcel_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* t, const int* fdefined_in, const float* ps, int fdef_ps,
+                         const float* alevel, const float* blevel, int from, int src_level, const float* t_src, int fdef_tsrc,
+                         const float* q_src, int fdef_qsrc, const float* p_src, int fdef_psrc, float* cape, float* cin, float* plcl,
+                         float* plfc, float* pel, float* tparcel, int* fdefined_out, float undef, int memkind);
+int mifc_vparcel_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* t, const int* fdefined_in, const float* p,
+                        const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, int from, int src_level, const float* t_src,
+                        int fdef_tsrc, const float* q_src, int fdef_qsrc, const float* p_src, int fdef_psrc, float* cape, float* cin,
+                        float* plcl, float* plfc, float* pel, float* tparcel, int* fdefined_out, float undef, int memkind);
+int mifc_vparcel_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* t, const int* fdefined_in,
+                        const float* levels /* HOST float[nlev] */, int from, int src_level, const float* t_src, int fdef_tsrc,
+                        const float* q_src, int fdef_qsrc, const float* p_src, int fdef_psrc, float* cape, float* cin, float* plcl,
+                        float* plfc, float* pel, float* tparcel, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_vparcel_form(void);
+
 /* ---- EXTENSION: level batches sampled at arbitrary points (regridding, cross-sections, soundings) ------------
  * Not a miutil::fieldcalc function: the reference's callers take a field to a flight route, a section line, a list of
  * stations or the grid of another projection on the host, level by level (their field class has an

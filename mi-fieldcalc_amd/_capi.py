@@ -138,6 +138,14 @@ SIGNATURES = {
     "mifc_vcumul_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
     "mifc_vcumul_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
     "mifc_last_vcumul_form": ("s", []),
+    # EXTENSION: parcel ascent over level batches (t: the batch itself; the six outputs: any may be None; fdefined_out: host int[5 + nlev])
+    "mifc_vparcel_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "p", "i", "p", "p", "i", "i", "p", "i", "p", "i", "p", "i",
+                                   "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
+    "mifc_vparcel_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "p", "pi", "i", "i", "p", "i", "p", "i", "p", "i",
+                                  "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
+    "mifc_vparcel_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "p", "i", "i", "p", "i", "p", "i", "p", "i",
+                                  "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
+    "mifc_last_vparcel_form": ("s", []),
     # EXTENSION: level batches sampled at arbitrary points (fields, fres: host tables of pointers; xpos, ypos: where the fields are)
     "mifc_hinterp_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_last_hinterp_form": ("s", []),

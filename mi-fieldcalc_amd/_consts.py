@@ -15,6 +15,9 @@ VDERIV_METHODS = {"centred": 0, "weighted": 1}
 # the methods and walk directions of mifc_vcumul_* (MIFC_VCUMUL_*)
 VCUMUL_METHODS = {"linear": 0, "log": 1}
 VCUMUL_FROM = {"first": 0, "last": 1}
+# the walk directions of mifc_vparcel_* (MIFC_VPARCEL_FROM_*) and the order of its outputs in the flags
+VPARCEL_FROM = {"first": 0, "last": 1}
+VPARCEL_OUTPUTS = ("cape", "cin", "plcl", "plfc", "pel", "tparcel")
 # miutil::constants r and g (MetConstants.h): the gas constant of dry air, J / (kg K), and gravity, m / s^2
 R_DRY, GRAVITY = 287.0, 9.8
 # the methods of mifc_hinterp_levels (MIFC_HINTERP_*)

@@ -466,6 +466,43 @@ struct VcumulParams
 };
 hipError_t launch_vcumul(const VcumulParams& prm, hipStream_t stream);
 
+// ------------------------------------ parcel ascent over level batches (mifc_vparcel.hip), EXTENSION
+// One launch walks `n` columns once, from level 0 upward in index (from = 0) or from level nlev - 1 downward (from = 1),
+// lifts the parcel of rules 1 to 9 of mifc_vparcel_* (include/mifc.h) from level to level and stores what is asked for:
+// planes[0 .. 4] = cape, cin, plcl, plfc, pel (n floats each) and tparcel (a batch: level k at tparcel + k * out_stride);
+// each may be null.  `t`, `coord`, `ab`, `lev_bits` (bit 0 = t is flagged ALL_DEFINED at level k, bit VINTERP_COORD_BIT =
+// the pressure batch is), vec4 and kind (VDERIV_HYBRID / _FIELD / _LEVELS) as in VcumulParams.  kind VDERIV_LEVELS:
+// lev_p[k] = levels[k] and lev_p[nlev + k] = pi_from_p(levels[k]), from the host.  src_level >= 0: the source is that
+// level with the humidity q_src; -1: the planes t_src, q_src, p_src (n floats each; *_all: flagged ALL_DEFINED).
+// Counters: n_undefined[0 .. 4] the planes, n_undefined[VPARCEL_PLANES + k] tparcel's level k, zeroed by the caller; a
+// workgroup gathers its counts in VPARCEL_PLANES + nlev words of dynamic LDS when lds_counts is set (the launcher sets it
+// where that fits), otherwise a wave adds to the global counters itself.
+const int VPARCEL_PLANES = 5;
+struct VparcelParams
+{
+  int kind; // VDERIV_HYBRID / VDERIV_FIELD / VDERIV_LEVELS
+  int from; // MIFC_VPARCEL_FROM_FIRST / MIFC_VPARCEL_FROM_LAST
+  int src_level;
+  int n;    // columns of this launch
+  int nlev; // >= 2
+  int vec4;
+  int ps_all; // hybrid: fdef_ps == ALL_DEFINED
+  int tsrc_all, qsrc_all, psrc_all;
+  int lds_counts; // set by launch_vparcel
+  float undef;
+  long in_stride, out_stride;
+  const float* t;
+  const float* coord;
+  const float *t_src, *q_src, *p_src;
+  float* planes[VPARCEL_PLANES];
+  float* tparcel;
+  const float* ab;
+  const unsigned int* lev_bits;
+  const float* lev_p;
+  u64* n_undefined;
+};
+hipError_t launch_vparcel(const VparcelParams& prm, hipStream_t stream);
+
 // ------------------------------------ level batches sampled at arbitrary points (mifc_hinterp.hip), EXTENSION
 // One launch samples `nlev` levels of up to hinterp_pass_fields(method) fields at `npos` points: a gather.  A lane owns
 // one point, a workgroup 256 consecutive points and the levels [blockIdx.y * chunk, + chunk) of the launch; level k of
