@@ -667,6 +667,58 @@ int mifc_vparcel_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* t,
                         float* plfc, float* pel, float* tparcel, int* fdefined_out, float undef, int memkind);
 const char* mifc_last_vparcel_form(void);
 
+/* ---- EXTENSION: Ertel potential vorticity of level batches ----------------------------------------------------
+ * Not a miutil::fieldcalc function: the one diagnostic that differences a level batch along all three axes, and the
+ * coordinate batch of the dynamic tropopause (mifc_vinterp_fields with PV as the coordinate and 2 PVU as the target).
+ * u, v, th (the wind components and the potential temperature), each [nlev][ny][nx], one coordinate p per level -- the
+ * three coordinate forms of mifc_vderiv_* above --, the map ratios xmapr = xm / (2 hx), ymapr = ym / (2 hy) of the
+ * reference's stencil operators and, optionally, fcoriolis go in ([ny][nx] each); fpv is [nlev][ny][nx].
+ * Per level k and cell (x, y): (xc, yc) = (clamp(x, 1, nx - 2), clamp(y, 1, ny - 2)), i = yc * nx + xc, and everything
+ * below is evaluated at i: the outer ring carries the value of its nearest interior cell, which is what the reference's
+ * fillEdges produces (FieldCalculations.cc:59-74).
+ *   1. Coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it, usable as in rule 1 of mifc_vderiv_*.
+ *   2. Vertical derivatives.  D_u, D_v, D_th at (k, i) are the double r of rules 2 to 6 of mifc_vderiv_* BEFORE its
+ *      rounding to float, each per field, with the call's method (MIFC_VDERIV_CENTRED / MIFC_VDERIV_WEIGHTED).  A field
+ *      whose derivative those rules leave undef (centre not usable, no side, zero denominator) makes the cell undef.
+ *   3. Horizontal terms, at level k, in the reference's arithmetic (FieldCalculations.cc:1862):
+ *      dx(a) = (0.5 * (double)xmapr[i]) * (double)(a[i + 1] - a[i - 1]),
+ *      dy(a) = (0.5 * (double)ymapr[i]) * (double)(a[i + nx] - a[i - nx]): the difference in float, the two products in
+ *      double.  Needed: dx(v), dy(u), dx(th), dy(th).  Each of the eight neighbour values must pass
+ *      is_defined(fdefined_in[f * nlev + k] == ALL_DEFINED, value, undef), otherwise the cell is undef.  xmapr, ymapr and
+ *      fcoriolis are not tested, as in the reference; the coordinate of the neighbours plays no part.
+ *   4. Product, in double, every operation rounded on its own, in this order: zeta = dx(v) - dy(u);
+ *      za = zeta + (double)fcoriolis[i] (fcoriolis == NULL: the addition is absent); t1 = za * D_th; t2 = D_v * dx(th);
+ *      t3 = D_u * dy(th); S = (t1 - t2) + t3.
+ *   5. Result.  (float)(scale * S).  A computed NaN or infinity is a value: not undef, not counted.
+ *   6. Flag.  fdefined_out[k] = checkDefined(interior cells left undef at level k, (nx - 2) * (ny - 2)); the ring is a
+ *      copy and is not counted.
+ * This is PV = -g [(f + zeta) dth/dp - dv/dp dth/dx + du/dp dth/dy] for scale = -g, the horizontal differences taken
+ * along the surfaces of the batch, so the formula holds on pressure, hybrid and any other levels; with p in hPa
+ * scale = -g * 1e4 gives PVU.  Bit for bit this definition (restated in numpy in tests/pvort_restate.py).
+ * `fdefined_in` HOST int[3 * nlev] in the order u, v, th, NULL = SOME_DEFINED; `fdefined_out` HOST int[nlev]; `alevel`,
+ * `blevel`, `levels` HOST float[nlev]; `fdef_coord` HOST int[nlev] or NULL.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; a negative nx or
+ * ny; nx < 3 or ny < 3 with a grid that is not empty (the reference's stencil operators return false there); an unknown
+ * method; a NaN scale; a null pointer that is required; hybrid form: a level whose (alevel, blevel) the reference's
+ * bad_hlevel rejects; `levels` form: a NaN level; fpv overlapping any input by byte range; a call made while a
+ * mifc_graph capture is open.  Zero cells: the flags are ALL_DEFINED, the call returns 1.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time with the
+ * neighbour rows it needs, MIFC_PVORT_CHUNK_MIB of device memory (default 256); the result does not depend on the bands.
+ * One launch walks the levels once per workgroup tile.  mifc_last_pvort_form: a diagnostic for tests,
+ * the calling thread's last call that launched: "v=4 kind=hybrid method=weighted tile=128x8 launches=1 bands=1". */
+int mifc_pvort_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* u, const float* v, const float* th,
+                       const int* fdefined_in /* HOST int[3 * nlev], order u, v, th; NULL = SOME_DEFINED */, const float* ps, int fdef_ps,
+                       const float* alevel, const float* blevel, const float* xmapr, const float* ymapr,
+                       const float* fcoriolis /* may be NULL */, int method, double scale, float* fpv, int* fdefined_out, float undef,
+                       int memkind);
+int mifc_pvort_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* u, const float* v, const float* th, const int* fdefined_in,
+                      const float* p, const int* fdef_coord /* HOST int[nlev] or NULL */, const float* xmapr, const float* ymapr,
+                      const float* fcoriolis, int method, double scale, float* fpv, int* fdefined_out, float undef, int memkind);
+int mifc_pvort_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* u, const float* v, const float* th, const int* fdefined_in,
+                      const float* levels /* HOST float[nlev] */, const float* xmapr, const float* ymapr, const float* fcoriolis, int method,
+                      double scale, float* fpv, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_pvort_form(void);
+
 /* ---- EXTENSION: level batches sampled at arbitrary points (regridding, cross-sections, soundings) ------------
  * Not a miutil::fieldcalc function: the reference's callers take a field to a flight route, a section line, a list of
  * stations or the grid of another projection on the host, level by level (their field class has an

@@ -25,6 +25,7 @@ _T = {
     "pu": ctypes.c_void_p,  # unsigned long long* (device)
     "z": ctypes.c_size_t,
     "u64": ctypes.c_ulonglong,
+    "d": ctypes.c_double,
 }
 
 # name -> (restype, [argument kinds]); mirrors include/mifc.h one to one
@@ -146,6 +147,11 @@ SIGNATURES = {
     "mifc_vparcel_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "p", "i", "i", "p", "i", "p", "i", "p", "i",
                                   "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),
     "mifc_last_vparcel_form": ("s", []),
+    # EXTENSION: Ertel potential vorticity of level batches (u, v, th; fcoriolis may be None; scale: a double)
+    "mifc_pvort_hlevels": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "pi", "p", "i", "p", "p", "p", "p", "p", "i", "d", "p", "pi", "f", "i"]),
+    "mifc_pvort_fields": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "pi", "p", "pi", "p", "p", "p", "i", "d", "p", "pi", "f", "i"]),
+    "mifc_pvort_levels": ("i", ["ctx", "i", "i", "i", "p", "p", "p", "pi", "p", "p", "p", "p", "i", "d", "p", "pi", "f", "i"]),
+    "mifc_last_pvort_form": ("s", []),
     # EXTENSION: level batches sampled at arbitrary points (fields, fres: host tables of pointers; xpos, ypos: where the fields are)
     "mifc_hinterp_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "i", "p", "p", "i", "p", "pi", "f", "i"]),
     "mifc_last_hinterp_form": ("s", []),

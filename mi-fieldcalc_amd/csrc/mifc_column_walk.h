@@ -1,5 +1,5 @@
 // mifc_column_walk.h -- what the kernels that walk the levels of a column have in common (mifc_vinterp.hip,
-// mifc_vlayer.hip, mifc_vderiv.hip, mifc_vcumul.hip, mifc_vparcel.hip): a lane owns V consecutive cells (four through 16-byte accesses, or one where the
+// mifc_vlayer.hip, mifc_vderiv.hip, mifc_vcumul.hip, mifc_vparcel.hip, mifc_pvort.hip): a lane owns V consecutive cells (four through 16-byte accesses, or one where the
 // batch is off the 16-byte grid) and keeps them for all levels, in level slots that rotate.  Device code only.
 #ifndef MIFC_COLUMN_WALK_H
 #define MIFC_COLUMN_WALK_H

@@ -29,6 +29,7 @@ struct Env
   int vderiv_chunk_mib = 0;       // MIFC_VDERIV_CHUNK_MIB (> 0): device staging of a host-memory mifc_vderiv_* call, a band of rows at a time (default 256); mifc_vrotate_levels too
   int vcumul_chunk_mib = 0;       // MIFC_VCUMUL_CHUNK_MIB (> 0): device staging of a host-memory mifc_vcumul_* call, a band of rows at a time (default 256)
   int vparcel_chunk_mib = 0;      // MIFC_VPARCEL_CHUNK_MIB (> 0): device staging of a host-memory mifc_vparcel_* call, a band of rows at a time (default 256)
+  int pvort_chunk_mib = 0;        // MIFC_PVORT_CHUNK_MIB (> 0): device staging of a host-memory mifc_pvort_* call, a band of rows and its neighbour rows at a time (default 256)
   int hinterp_chunk_mib = 0;      // MIFC_HINTERP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hinterp_levels call, whole levels at a time (default 256); mifc_hinterp_vector_levels too
   int hstats_chunk_mib = 0;       // MIFC_HSTATS_CHUNK_MIB (> 0): device staging of a host-memory mifc_hstats_levels call, a band of rows at a time (default 256)
   int hinterp_level_chunk = 0;    // MIFC_HINTERP_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the hinterp and vrotate kernels walks; A/B, tests)

@@ -57,6 +57,7 @@ void env_reload()
   e.vderiv_chunk_mib = positive_int("MIFC_VDERIV_CHUNK_MIB");
   e.vcumul_chunk_mib = positive_int("MIFC_VCUMUL_CHUNK_MIB");
   e.vparcel_chunk_mib = positive_int("MIFC_VPARCEL_CHUNK_MIB");
+  e.pvort_chunk_mib = positive_int("MIFC_PVORT_CHUNK_MIB");
   e.hinterp_chunk_mib = positive_int("MIFC_HINTERP_CHUNK_MIB");
   e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
   e.hinterp_level_chunk = positive_int("MIFC_HINTERP_LEVEL_CHUNK");

@@ -503,6 +503,40 @@ struct VparcelParams
 };
 hipError_t launch_vparcel(const VparcelParams& prm, hipStream_t stream);
 
+// ------------------------------------ Ertel potential vorticity of level batches (mifc_pvort.hip), EXTENSION
+// One launch walks the `nlev` levels of a block of rows once.  The planes of the launch hold `rows` rows of nx cells: row
+// 0 of them is row g0 of the call's grid of ny rows (device memory: g0 = 0, rows = ny; a staged band: the rows it owns
+// and the neighbour rows they need).  The workgroup tiles cover the columns 0 .. nx - 1 and the rows c0 .. c1 (grid
+// rows, all of them interior: 1 <= c0, c1 <= ny - 2, and c0 - 1 .. c1 + 1 lie in the planes); a computed row y is stored
+// to y where own0 <= y < own1, to row 0 where y == 1 and own0 == 0, and to row ny - 1 where y == ny - 2 and own1 == ny.
+// Level k of a batch lies k * stride floats behind its pointer (inputs and output alike).  kind, ab, lev_bits (bits 0, 1,
+// 2: u, v, th flagged ALL_DEFINED at level k), lev_w and vec4 as in VderivParams; vec4 needs nx % 4 == 0 too.
+// Counters: n_undefined[k], zeroed by the caller, one atomic per workgroup and level with something to count.
+const int PVORT_LANES_X = 32, PVORT_TILE_ROWS = 8;
+struct PvortParams
+{
+  int kind;   // VDERIV_HYBRID / VDERIV_FIELD / VDERIV_LEVELS
+  int method; // MIFC_VDERIV_CENTRED / MIFC_VDERIV_WEIGHTED
+  int nx, ny, nlev;
+  int g0, rows;
+  int c0, c1;
+  int own0, own1;
+  int vec4;
+  int ps_all; // hybrid: fdef_ps == ALL_DEFINED
+  float undef;
+  double scale;
+  long stride;
+  const float *u, *v, *th;
+  const float* coord; // ps [rows][nx], the coordinate batch, or null (levels)
+  const float *xmapr, *ymapr, *fcoriolis; // [rows][nx]; fcoriolis may be null
+  float* out;
+  const float* ab;
+  const unsigned int* lev_bits;
+  const double* lev_w;
+  u64* n_undefined;
+};
+hipError_t launch_pvort(const PvortParams& prm, hipStream_t stream);
+
 // ------------------------------------ level batches sampled at arbitrary points (mifc_hinterp.hip), EXTENSION
 // One launch samples `nlev` levels of up to hinterp_pass_fields(method) fields at `npos` points: a gather.  A lane owns
 // one point, a workgroup 256 consecutive points and the levels [blockIdx.y * chunk, + chunk) of the launch; level k of
