@@ -157,9 +157,8 @@ int mifc_hstats_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* const
   form.tested = P.tested;
   form.products = products;
   form.segs = segs;
-  size_t band_row0 = 0; // the grid row of the planes' row 0
-  const int ran = plan.run(c, a, [&](int n) {
-    const size_t band_rows = (size_t)n / (size_t)nx;
+  const int ran = plan.run(c, a, [&](const BandRows& band) {
+    const size_t band_row0 = (size_t)band.first, band_rows = (size_t)band.staged; // the grid row of the planes' row 0, their rows
     const size_t lo = std::max(band_row0, (size_t)j0), hi = std::min(band_row0 + band_rows, (size_t)j1); // the box's rows in this band
     form.bands += 1;
     if (lo < hi) {
@@ -179,7 +178,6 @@ int mifc_hstats_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* const
       }
       form.blocks = mifc::hstats_plan(P.rows, segs, nlev).blocks;
     }
-    band_row0 += band_rows;
     return 1;
   });
   if (!ran)

@@ -1,13 +1,13 @@
 // mifc_capi_pvort.hip -- C ABI of mifc_pvort_hlevels / mifc_pvort_fields / mifc_pvort_levels (include/mifc.h;
 // EXTENSION, no reference function) on the level-batch driver (mifc_levelbatch.h): the head of the call with the three
 // fields u, v, th, its refusals, the level table with one counter per level and, for the `levels` form, the weights of
-// mifc_vderiv_levels in its tail.  Device memory is used in place.  Host memory is staged band by band, but a band of
-// rows is no complete problem here: a band carries the neighbour rows its rows need (rows 0 and ny - 1 those of rows 1
-// and ny - 2), only the rows it owns are downloaded.  That loop is this file's own (BandPlan knows no halo).  Every cell
-// is computed by the same arithmetic whichever band it falls into, so the result does not depend on the bands.
+// mifc_vderiv_levels in its tail (vderiv_level_weights).  Device memory is used in place.  Host memory is staged band by
+// band, but a band of rows is no complete problem here: the BandPlan is placed with a halo of one row, so a band carries
+// the neighbour rows its rows need (rows 0 and ny - 1 those of rows 1 and ny - 2) and only the rows it owns are
+// downloaded.  Every cell is computed by the same arithmetic whichever band it falls into, so the result does not depend
+// on the bands.
 #include "mifc_levelbatch.h"
 
-#include <cstdint>
 #include <cstdio>
 
 using namespace mifc_host;
@@ -80,42 +80,23 @@ int run(mifc_ctx* c, const Call& call, const float* u, const float* v, const flo
   LevelTable tab; // one counter per level; `levels`: the four weights of mifc_vderiv_levels per level in the tail
   if (!tab.build(c, a, (size_t)nlev, by_level ? 4 * (size_t)nlev * sizeof(double) : 0))
     return 0;
-  if (by_level) {
-    // rules 3 to 5 of mifc_vderiv_* for a coordinate that is the same in every cell of a level, as mifc_capi_vderiv.hip
-    // has them: in double, every operation rounded on its own (this file is compiled without contraction like the kernels)
-    double* w = static_cast<double*>(tab.tail());
-    const float* lv = a.coord;
-    for (int k = 0; k < nlev; ++k) {
-      const bool lower = k > 0 && lv[k - 1] != lv[k], upper = k < nlev - 1 && lv[k + 1] != lv[k];
-      const double d0 = (double)lv[k], dm = k > 0 ? (double)lv[k - 1] : 0.0, dp = k < nlev - 1 ? (double)lv[k + 1] : 0.0;
-      const double h1 = d0 - dm, h2 = dp - d0;
-      if (lower)
-        w[4 * k] = 1.0 / h1;
-      if (upper)
-        w[4 * k + 1] = 1.0 / h2;
-      bool fold = false;
-      if (lower && upper) {
-        if (call.method == MIFC_VDERIV_WEIGHTED) {
-          const double s = h1 + h2;
-          fold = s == 0.0;
-          if (!fold) {
-            const double p1 = h1 * s, p2 = h2 * s;
-            w[4 * k + 2] = h2 / p1;
-            w[4 * k + 3] = h1 / p2;
-          }
-        } else {
-          const double dc = dp - dm;
-          fold = dc == 0.0;
-          if (!fold)
-            w[4 * k + 2] = 1.0 / dc;
-        }
-      }
-      tab.bits()[k] |= (lower ? 1u << mifc::VDERIV_LOWER_BIT : 0u) | (upper ? 1u << mifc::VDERIV_UPPER_BIT : 0u) |
-                       (fold ? 1u << mifc::VDERIV_FOLD_BIT : 0u);
-    }
-  }
+  if (by_level)
+    vderiv_level_weights(tab, a, call.method);
   Staging st(c, a.memkind); // blocks only: a host batch is staged band by band
   if (!tab.upload(c, st))
+    return 0;
+
+  // u, v, th | the coordinate | xmapr, ymapr, fcoriolis | fpv; a band of host memory carries one neighbour row on each side
+  BandPlan plan;
+  PlaneGroup* const gu = plan.in(u, (size_t)nlev);
+  PlaneGroup* const gv = plan.in(v, (size_t)nlev);
+  PlaneGroup* const gth = plan.in(th, (size_t)nlev);
+  PlaneGroup* const coord = plan.in(a.coord, a.coord_planes()); // (`levels`: no planes, null)
+  PlaneGroup* const gxm = plan.in(call.xmapr, 1);
+  PlaneGroup* const gym = plan.in(call.ymapr, 1);
+  PlaneGroup* const gf = plan.in(call.fcoriolis, 1);
+  PlaneGroup* const gout = plan.out(call.fpv, (size_t)nlev);
+  if (!plan.place(c, st, a, (size_t)(mifc::env().pvort_chunk_mib > 0 ? mifc::env().pvort_chunk_mib : 256) << 20, 1))
     return 0;
 
   mifc::PvortParams P;
@@ -132,95 +113,38 @@ int run(mifc_ctx* c, const Call& call, const float* u, const float* v, const flo
   P.lev_bits = tab.lev_bits();
   P.lev_w = static_cast<const double*>(tab.dev_tail());
   P.n_undefined = tab.n_undefined();
+  P.u = gu->dev;
+  P.v = gv->dev;
+  P.th = gth->dev;
+  P.coord = coord->dev;
+  P.xmapr = gxm->dev;
+  P.ymapr = gym->dev;
+  P.fcoriolis = gf->dev;
+  P.out = gout->dev;
+  P.stride = plan.stride;
+  P.vec4 = plan.vec4 && (nx & 3) == 0 ? 1 : 0; // (whole rows on the 16-byte grid, which the plan does not ask for)
 
-  int launches = 0, bands = 0;
-  if (a.memkind != MIFC_MEM_HOST) {
-    // the caller's planes: one launch over all rows
-    uintptr_t all = reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(th) |
-                    reinterpret_cast<uintptr_t>(call.xmapr) | reinterpret_cast<uintptr_t>(call.ymapr) | reinterpret_cast<uintptr_t>(call.fcoriolis) |
-                    reinterpret_cast<uintptr_t>(call.fpv);
-    if (!by_level)
-      all |= reinterpret_cast<uintptr_t>(a.coord);
-    P.u = u;
-    P.v = v;
-    P.th = th;
-    P.coord = by_level ? nullptr : a.coord;
-    P.xmapr = call.xmapr;
-    P.ymapr = call.ymapr;
-    P.fcoriolis = call.fcoriolis;
-    P.out = call.fpv;
-    P.stride = (long)cells;
-    P.vec4 = ((nx & 3) == 0 && (all & 15) == 0) ? 1 : 0;
-    P.g0 = 0;
-    P.rows = ny;
-    P.c0 = 1;
-    P.c1 = ny - 2;
-    P.own0 = 0;
-    P.own1 = ny;
+  // one launch over the rows of a problem: the interior rows among its own, and the ring rows beside them
+  int launches = 0;
+  auto launch = [&](const BandRows& rows) -> int {
+    P.own0 = rows.own0;
+    P.own1 = rows.own1;
+    P.c0 = clamp_row(rows.own0, ny);
+    P.c1 = clamp_row(rows.own1 - 1, ny);
+    P.g0 = rows.first;
+    P.rows = rows.staged;
     MIFC_LAUNCH(c, mifc::launch_pvort(P, c->stream));
-    launches = bands = 1;
-  } else {
-    // u, v, th | the coordinate | xmapr, ymapr, fcoriolis | fpv, one behind the other in one block; a band owns `own`
-    // rows and is staged with the rows around them, `staged` at most
-    const size_t coord_planes = a.coord_planes(), n_map = call.fcoriolis ? 3 : 2;
-    const size_t planes = 4 * (size_t)nlev + coord_planes + n_map;
-    const size_t budget = (size_t)(mifc::env().pvort_chunk_mib > 0 ? mifc::env().pvort_chunk_mib : 256) << 20;
-    const size_t staged = std::min<size_t>((size_t)ny, std::max<size_t>(3, plan_band(budget, planes, (size_t)nx, (size_t)ny).rows));
-    const size_t own = staged >= (size_t)ny ? (size_t)ny : staged - 2;
-    const size_t S = align_up(staged * (size_t)nx, 64);
-    float* d = static_cast<float*>(st.scratch(planes * S * sizeof(float)));
-    if (!st.ok())
-      return 0;
-    struct Group
-    {
-      const float* host;
-      float* dev;
-      size_t planes;
-    };
-    Group in[7] = {{u, nullptr, (size_t)nlev}, {v, nullptr, (size_t)nlev}, {th, nullptr, (size_t)nlev}, {by_level ? nullptr : a.coord, nullptr, coord_planes},
-                   {call.xmapr, nullptr, 1},   {call.ymapr, nullptr, 1},   {call.fcoriolis, nullptr, call.fcoriolis ? (size_t)1 : 0}};
-    for (Group& g : in) {
-      g.dev = g.planes ? d : nullptr;
-      d += g.planes * S;
-    }
-    float* const dev_out = d;
-    P.u = in[0].dev;
-    P.v = in[1].dev;
-    P.th = in[2].dev;
-    P.coord = in[3].dev;
-    P.xmapr = in[4].dev;
-    P.ymapr = in[5].dev;
-    P.fcoriolis = in[6].dev;
-    P.out = dev_out;
-    P.stride = (long)S;
-    P.vec4 = (nx & 3) == 0 ? 1 : 0; // (the block and S are on the 16-byte grid)
-    const size_t pitch = plane, dpitch = S * sizeof(float);
-    for (size_t r0 = 0; r0 < (size_t)ny; r0 += own) {
-      const int own0 = (int)r0, own1 = (int)std::min(r0 + own, (size_t)ny);
-      P.own0 = own0;
-      P.own1 = own1;
-      P.c0 = clamp_row(own0, ny);
-      P.c1 = clamp_row(own1 - 1, ny);
-      P.g0 = P.c0 - 1;
-      P.rows = P.c1 + 1 - P.g0 + 1;
-      const size_t width = (size_t)P.rows * (size_t)nx * sizeof(float), off = (size_t)P.g0 * (size_t)nx;
-      for (const Group& g : in)
-        if (g.dev)
-          MIFC_HIP(c, hipMemcpy2DAsync(g.dev, dpitch, g.host + off, pitch, width, g.planes, hipMemcpyHostToDevice, c->stream));
-      MIFC_LAUNCH(c, mifc::launch_pvort(P, c->stream));
-      const size_t mine = (size_t)own0 * (size_t)nx;
-      MIFC_HIP(c, hipMemcpy2DAsync(call.fpv + mine, pitch, dev_out + (mine - off), dpitch, (size_t)(own1 - own0) * (size_t)nx * sizeof(float), (size_t)nlev,
-                                   hipMemcpyDeviceToHost, c->stream));
-      launches += 1;
-      bands += 1;
-    }
-  }
+    launches += 1;
+    return 1;
+  };
+  if (!plan.run(c, a, launch))
+    return 0;
   if (!tab.read_counts(c) || !st.finish()) // finish(): the one synchronisation of the call
     return 0;
   const size_t interior = (size_t)(nx - 2) * (size_t)(ny - 2);
   for (int k = 0; k < nlev; ++k)
     call.fdefined_out[k] = tab.classify((size_t)k, interior);
-  t_form = {P.vec4 ? 4 : 1, a.kind, call.method == MIFC_VDERIV_WEIGHTED ? 1 : 0, launches, bands};
+  t_form = {P.vec4 ? 4 : 1, a.kind, call.method == MIFC_VDERIV_WEIGHTED ? 1 : 0, launches, launches}; // (a band is one launch)
   return 1;
 }
 

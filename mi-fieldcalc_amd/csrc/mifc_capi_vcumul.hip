@@ -121,10 +121,10 @@ int run(mifc_ctx* c, const Call& call)
   P.start_all = call.fdef_start == MIFC_ALL_DEFINED ? 1 : 0;
   P.lev_g = static_cast<const double*>(tab.dev_tail());
 
-  // the launches of one problem of n columns: four fields each
+  // the launches of one problem of rows.n() columns: four fields each
   int launches = 0;
-  auto launch_passes = [&](int n) -> int {
-    P.n = n;
+  auto launch_passes = [&](const BandRows& rows) -> int {
+    P.n = rows.n();
     for (int f0 = 0; f0 < nf; f0 += mifc::VCUMUL_PASS) {
       P.f0 = f0;
       P.nfields = std::min(mifc::VCUMUL_PASS, nf - f0);

@@ -1,7 +1,7 @@
 // mifc_capi_vderiv.hip -- C ABI of mifc_vderiv_hlevels / mifc_vderiv_fields / mifc_vderiv_levels (include/mifc.h;
 // EXTENSION, no reference function) on the level-batch driver (mifc_levelbatch.h): its own refusals, for the `levels`
-// form the weights (divided here once per level, in the tail of the device table), two or four fields per launch of the
-// kernel of mifc_vderiv.hip (vderiv_pass_fields).
+// form the weights in the tail of the device table (vderiv_level_weights), two or four fields per launch of the kernel
+// of mifc_vderiv.hip (vderiv_pass_fields).
 #include "mifc_levelbatch.h"
 
 using namespace mifc_host;
@@ -64,40 +64,8 @@ int run(mifc_ctx* c, const Call& call)
   LevelTable tab; // the counters of the derivatives, then those of the magnitudes; `levels`: four weights per level in the tail
   if (!tab.build(c, a, (size_t)(nf + nm) * (size_t)nlev, by_level ? 4 * (size_t)nlev * sizeof(double) : 0))
     return 0;
-  if (by_level) {
-    // rules 3 to 5 for a coordinate that is the same in every cell of a level: the sides that exist and the weights, in
-    // double, every operation rounded on its own (this file is compiled without contraction like the kernels)
-    double* w = static_cast<double*>(tab.tail());
-    const float* lv = a.coord;
-    for (int k = 0; k < nlev; ++k) {
-      const bool lower = k > 0 && lv[k - 1] != lv[k], upper = k < nlev - 1 && lv[k + 1] != lv[k];
-      const double d0 = (double)lv[k], dm = k > 0 ? (double)lv[k - 1] : 0.0, dp = k < nlev - 1 ? (double)lv[k + 1] : 0.0;
-      const double h1 = d0 - dm, h2 = dp - d0;
-      if (lower)
-        w[4 * k] = 1.0 / h1;
-      if (upper)
-        w[4 * k + 1] = 1.0 / h2;
-      bool fold = false;
-      if (lower && upper) {
-        if (call.method == MIFC_VDERIV_WEIGHTED) {
-          const double s = h1 + h2;
-          fold = s == 0.0;
-          if (!fold) {
-            const double p1 = h1 * s, p2 = h2 * s;
-            w[4 * k + 2] = h2 / p1;
-            w[4 * k + 3] = h1 / p2;
-          }
-        } else {
-          const double dc = dp - dm;
-          fold = dc == 0.0;
-          if (!fold)
-            w[4 * k + 2] = 1.0 / dc;
-        }
-      }
-      tab.bits()[k] |= (lower ? 1u << mifc::VDERIV_LOWER_BIT : 0u) | (upper ? 1u << mifc::VDERIV_UPPER_BIT : 0u) |
-                       (fold ? 1u << mifc::VDERIV_FOLD_BIT : 0u);
-    }
-  }
+  if (by_level)
+    vderiv_level_weights(tab, a, call.method);
   Staging st(c, a.memkind); // blocks only: a host batch is staged band by band
   if (!tab.upload(c, st))
     return 0;
@@ -121,10 +89,10 @@ int run(mifc_ctx* c, const Call& call)
   P.n_undefined_mag = P.n_undefined + (size_t)nf * (size_t)nlev;
   P.lev_w = static_cast<const double*>(tab.dev_tail());
 
-  // the launches of one problem of n columns: four fields each, two where both the derivatives and the magnitudes are
+  // the launches of one problem of rows.n() columns: four fields each, two where both the derivatives and the magnitudes are
   // written (an even number: a vector stays in one launch)
-  auto launch_passes = [&](int n) -> int {
-    P.n = n;
+  auto launch_passes = [&](const BandRows& rows) -> int {
+    P.n = rows.n();
     const int pass = mifc::vderiv_pass_fields(P.what);
     for (int f0 = 0; f0 < nf; f0 += pass) {
       P.f0 = f0;

@@ -78,9 +78,9 @@ int run(mifc_ctx* c, const Call& call)
     P.out[f] = out[f]->dev;
   }
 
-  // the launches of one problem of n columns: 32 targets each
-  auto launch_passes = [&](int n) -> int {
-    P.n = n;
+  // the launches of one problem of rows.n() columns: 32 targets each
+  auto launch_passes = [&](const BandRows& rows) -> int {
+    P.n = rows.n();
     for (int t0 = 0; t0 < nt; t0 += mifc::VINTERP_PASS) {
       P.t0 = t0;
       P.nt = std::min(mifc::VINTERP_PASS, nt - t0);

@@ -84,9 +84,9 @@ int run(mifc_ctx* c, const Call& call)
   P.lo_field = lo->dev;
   P.hi_field = hi->dev;
 
-  // the launches of one problem of n columns: vlayer_pass_fields(group) fields each
-  auto launch_passes = [&](int n) -> int {
-    P.n = n;
+  // the launches of one problem of rows.n() columns: vlayer_pass_fields(group) fields each
+  auto launch_passes = [&](const BandRows& rows) -> int {
+    P.n = rows.n();
     const int pass = mifc::vlayer_pass_fields(group);
     for (int f0 = 0; f0 < nf; f0 += pass) {
       P.f0 = f0;

@@ -150,8 +150,8 @@ int run(mifc_ctx* c, const float* t, const Call& call)
   P.lev_p = static_cast<const float*>(tab.dev_tail());
 
   int launches = 0;
-  auto launch = [&](int n) -> int {
-    P.n = n;
+  auto launch = [&](const BandRows& rows) -> int {
+    P.n = rows.n();
     MIFC_LAUNCH(c, mifc::launch_vparcel(P, c->stream));
     launches += 1;
     return 1;

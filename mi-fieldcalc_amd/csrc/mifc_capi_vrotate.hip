@@ -94,10 +94,10 @@ int mifc_vrotate_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* cons
   form.v = plan.vec4 ? 4 : 1;
   form.np = npairs;
   form.tested = P.tested;
-  auto launch = [&](int n) -> int { // one problem of n cells
-    P.n = n;
+  auto launch = [&](const BandRows& rows) -> int { // one problem of rows.n() cells
+    P.n = rows.n();
     MIFC_LAUNCH(c, mifc::launch_vrotate(P, c->stream));
-    const mifc::VrotatePlan shape = mifc::vrotate_plan(n, nlev, P.vec4);
+    const mifc::VrotatePlan shape = mifc::vrotate_plan(P.n, nlev, P.vec4);
     form.blocks = shape.blocks;
     form.level_chunks = shape.level_chunks;
     form.chunk = shape.chunk;

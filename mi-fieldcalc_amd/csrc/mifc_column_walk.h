@@ -4,6 +4,8 @@
 #ifndef MIFC_COLUMN_WALK_H
 #define MIFC_COLUMN_WALK_H
 
+#include "mifc_kernels.h"
+
 #include <hip/hip_runtime.h>
 
 namespace mifc {
@@ -77,6 +79,47 @@ struct WalkLevel
   float c[V]; // field coordinate: as loaded
   float x[NF][V];
 };
+
+// The coordinate of a level in the lane's cells, with "not usable" carried as NaN (a NaN never brackets, differs from
+// everything and fails every ordered compare, so no flag per cell has to live through the walk).  KIND: VDERIV_HYBRID =
+// alevel + blevel * ps, VDERIV_FIELD = a batch like the fields, VDERIV_LEVELS = one number per level, nothing per cell.
+// walk_usable_ps: ps as loaded -> ps for walk_coordinate (an undefined ps: every level of the cell is not usable).
+template <int V>
+__device__ __forceinline__ void walk_usable_ps(float (&ps)[V], bool ps_all, float undef)
+{
+  const float nan = __int_as_float(0x7fc00000);
+#pragma unroll
+  for (int c = 0; c < V; ++c) {
+    const float p = ps[c]; // (read first: the test below then selects, it does not branch around a load)
+    ps[c] = (ps_all || p != undef) ? p : nan;
+  }
+}
+// level k: `lc` = the coordinate field's cells as loaded (VDERIV_FIELD), `bits` = the level's word of the table
+template <int KIND, int V>
+__device__ __forceinline__ void walk_coordinate(float (&cc)[V], const float (&lc)[V], const float (&ps)[V], ConstFloats ab, int nlev, int k, unsigned int bits,
+                                                float undef)
+{
+  if constexpr (KIND == VDERIV_HYBRID) {
+    const float a = ab[k], b = ab[nlev + k];
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+      const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
+      cc[c] = a + prod;
+    }
+  } else if constexpr (KIND == VDERIV_FIELD) {
+    const float nan = __int_as_float(0x7fc00000);
+    const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+      const float x = lc[c]; // (read first, as in walk_usable_ps)
+      cc[c] = (all || x != undef) ? x : nan;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < V; ++c)
+      cc[c] = 0.f; // not used: the table says which sides exist
+  }
+}
 
 } // namespace
 

@@ -1,9 +1,10 @@
 // mifc_levelbatch.h -- the host driver of the entries that walk level batches column by column (mifc_capi_vinterp.hip,
 // mifc_capi_vlayer.hip, mifc_capi_vderiv.hip, mifc_capi_vcumul.hip, mifc_capi_vparcel.hip; the head, the refusals and the level table also serve
-// mifc_capi_hinterp.hip, which samples the levels instead of walking them, and mifc_capi_pvort.hip, whose bands carry neighbour rows): the head of such a call and the refusals
-// that read only it, the overlap rule, the device table of the per-level scalars, and where the planes of the call are on the device --
-// the caller's own for device memory, a band of rows at a time for host memory (columns are independent, so a band of
-// every level is a complete problem).  Implemented in mifc_levelbatch.hip.
+// mifc_capi_hinterp.hip, which samples the levels instead of walking them; mifc_capi_pvort.hip differences along the rows too, its bands carry neighbour rows): the head of such a call and the refusals
+// that read only it, the overlap rule, the device table of the per-level scalars (for the `levels` form of the vertical
+// derivative its weights too), and where the planes of the call are on the device -- the caller's own for device memory, a
+// band of rows at a time for host memory (columns are independent, so a band of every level is a complete problem; where
+// rows are not, a band is staged with the neighbour rows it needs).  Implemented in mifc_levelbatch.hip.
 #ifndef MIFC_LEVELBATCH_H
 #define MIFC_LEVELBATCH_H
 
@@ -91,18 +92,21 @@ private:
   unsigned char* dev_ = nullptr;
 };
 
-// The rows of a staged band and the floats between its planes (a multiple of 64: every plane on the 16-byte grid), so
-// that `planes` of them fit `budget` bytes -- but never less than one row.
-struct Band
-{
-  size_t rows, S;
-};
-inline Band plan_band(size_t budget, size_t planes, size_t nx, size_t ny)
+// Rules 3 to 5 of mifc_vderiv_* (include/mifc.h) for a coordinate that is the same in every cell of a level (COORD_LEVELS,
+// a.coord = levels[nlev], none of them NaN: the caller has refused that): the sides that exist and the weights, divided
+// once per level in double, every operation rounded on its own (mifc_levelbatch.hip is compiled without contraction like
+// the kernels).  Into the tail of `tab`, built with 4 * nlev doubles of it: 1 / (c_k - c_k-1), 1 / (c_k+1 - c_k) and the
+// two-sided weights of `method` per level; VDERIV_LOWER_BIT / _UPPER_BIT / _FOLD_BIT are added to the level's word.
+void vderiv_level_weights(LevelTable& tab, const LevelBatchCall& a, int method);
+
+// The rows of a staged band such that `planes` planes of them, each padded to a multiple of 64 floats (every plane on the
+// 16-byte grid), fit `budget` bytes -- but never less than one row.
+inline size_t plan_band(size_t budget, size_t planes, size_t nx, size_t ny)
 {
   size_t rows = std::max<size_t>(1, std::min<size_t>(ny, budget / (planes * nx * sizeof(float))));
   while (rows > 1 && planes * align_up(rows * nx, 64) * sizeof(float) > budget)
     rows -= 1;
-  return {rows, align_up(rows * nx, 64)};
+  return rows;
 }
 
 // The planes of a call, in groups that lie [planes][ny][nx] at `host`: uploaded (in) or downloaded (out) per band in the
@@ -114,6 +118,13 @@ struct PlaneGroup
   size_t planes;
   bool out;
 };
+// The rows of one problem of BandPlan::run(): the planes on the device hold the grid rows first .. first + staged - 1, the
+// rows own0 .. own1 - 1 of them are this problem's to write (device memory: all ny rows, staged and owned).
+struct BandRows
+{
+  int nx, first, staged, own0, own1;
+  int n() const { return staged * nx; } // the cells of a plane
+};
 class BandPlan
 {
 public:
@@ -121,28 +132,37 @@ public:
   PlaneGroup* out(float* host, size_t planes) { return add(host, planes, true); }
   // device memory: dev = host, the stride a level, vec4 where every pointer and the level size allow 16-byte accesses;
   // host memory: the groups one behind the other in one block of `budget` bytes at most, the stride S, vec4 (a lane's four
-  // floats may straddle the end of the band: they stay inside the padded plane)
-  int place(mifc_ctx* c, Staging& st, const LevelBatchCall& a, size_t budget);
+  // floats may straddle the end of the band: they stay inside the padded plane).
+  // halo_rows = 0: columns are independent, a band of rows is a complete problem.  halo_rows = h > 0 (ny >= 2 h + 1): a
+  // row needs its h neighbours on each side, the rows 0 .. h - 1 and ny - h .. ny - 1 are written from the rows next to
+  // them; a band is staged with the rows its own rows need -- at least 2 h + 1 rows whatever the budget says, the stride
+  // is their padded size -- and owns what is left of them, or everything where all ny rows fit.
+  int place(mifc_ctx* c, Staging& st, const LevelBatchCall& a, size_t budget, int halo_rows = 0);
   long stride = 0;
   int vec4 = 0;
-  // launch(n): the launches of one problem of n columns, 0 where one failed.  Host memory: per band the in-groups up,
-  // launch, the out-groups down.
+  // launch(rows): the launches of one problem (BandRows), 0 where one failed.  Host memory: per band the in-groups up over
+  // the staged rows, launch, the owned rows of the out-groups down.
   template <class Launch>
   int run(mifc_ctx* c, const LevelBatchCall& a, Launch launch)
   {
+    const int nx = a.nx, ny = a.ny, h = halo_;
     if (a.memkind != MIFC_MEM_HOST)
-      return launch((int)a.cells());
-    const size_t nx = (size_t)a.nx, pitch = a.cells() * sizeof(float), dpitch = (size_t)stride * sizeof(float);
-    for (size_t r0 = 0; r0 < (size_t)a.ny; r0 += rows_) {
-      const size_t n = std::min(rows_, (size_t)a.ny - r0) * nx, width = n * sizeof(float), off = r0 * nx;
+      return launch(BandRows{nx, 0, ny, 0, ny});
+    const size_t pitch = a.cells() * sizeof(float), dpitch = (size_t)stride * sizeof(float);
+    for (int r0 = 0; r0 < ny; r0 += own_) {
+      // the band's own rows, clamped to the rows that have all their neighbours, and the h rows around those
+      const int r1 = std::min(r0 + own_, ny), lo = std::min(std::max(r0, h), ny - 1 - h), hi = std::min(std::max(r1 - 1, h), ny - 1 - h);
+      const BandRows b = {nx, lo - h, hi - lo + 1 + 2 * h, r0, r1};
+      const size_t off = (size_t)b.first * (size_t)nx, mine = (size_t)r0 * (size_t)nx;
       for (int i = 0; i < n_; ++i)
         if (g_[i].dev && !g_[i].out)
-          MIFC_HIP(c, hipMemcpy2DAsync(g_[i].dev, dpitch, g_[i].host + off, pitch, width, g_[i].planes, hipMemcpyHostToDevice, c->stream));
-      if (!launch((int)n))
+          MIFC_HIP(c, hipMemcpy2DAsync(g_[i].dev, dpitch, g_[i].host + off, pitch, (size_t)b.n() * sizeof(float), g_[i].planes, hipMemcpyHostToDevice, c->stream));
+      if (!launch(b))
         return 0;
       for (int i = 0; i < n_; ++i)
         if (g_[i].dev && g_[i].out)
-          MIFC_HIP(c, hipMemcpy2DAsync(g_[i].host + off, pitch, g_[i].dev, dpitch, width, g_[i].planes, hipMemcpyDeviceToHost, c->stream));
+          MIFC_HIP(c, hipMemcpy2DAsync(g_[i].host + mine, pitch, g_[i].dev + (mine - off), dpitch, (size_t)(r1 - r0) * (size_t)nx * sizeof(float), g_[i].planes,
+                                       hipMemcpyDeviceToHost, c->stream));
     }
     return 1;
   }
@@ -156,7 +176,7 @@ private:
   static const int MAX_GROUPS = 28; // 8 fields, the coordinate, two bounds, 8 + 4 outputs; or a start, 8 bases and 8 outputs
   PlaneGroup g_[MAX_GROUPS];
   int n_ = 0;
-  size_t rows_ = 0;
+  int own_ = 0, halo_ = 0; // host memory: the rows a band owns, the neighbour rows on each side
 };
 
 // What VinterpParams, VlayerParams, VderivParams and VcumulParams have alike, everything else zero.

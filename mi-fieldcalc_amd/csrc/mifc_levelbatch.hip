@@ -130,7 +130,41 @@ int LevelTable::read_counts(mifc_ctx* c)
   return 1;
 }
 
-int BandPlan::place(mifc_ctx* c, Staging& st, const LevelBatchCall& a, size_t budget)
+void vderiv_level_weights(LevelTable& tab, const LevelBatchCall& a, int method)
+{
+  const int nlev = a.nlev;
+  const float* lv = a.coord;
+  double* w = static_cast<double*>(tab.tail());
+  for (int k = 0; k < nlev; ++k) {
+    const bool lower = k > 0 && lv[k - 1] != lv[k], upper = k < nlev - 1 && lv[k + 1] != lv[k];
+    const double d0 = (double)lv[k], dm = k > 0 ? (double)lv[k - 1] : 0.0, dp = k < nlev - 1 ? (double)lv[k + 1] : 0.0;
+    const double h1 = d0 - dm, h2 = dp - d0;
+    if (lower)
+      w[4 * k] = 1.0 / h1;
+    if (upper)
+      w[4 * k + 1] = 1.0 / h2;
+    bool fold = false;
+    if (lower && upper) {
+      if (method == MIFC_VDERIV_WEIGHTED) {
+        const double s = h1 + h2;
+        fold = s == 0.0;
+        if (!fold) {
+          const double p1 = h1 * s, p2 = h2 * s;
+          w[4 * k + 2] = h2 / p1;
+          w[4 * k + 3] = h1 / p2;
+        }
+      } else {
+        const double dc = dp - dm;
+        fold = dc == 0.0;
+        if (!fold)
+          w[4 * k + 2] = 1.0 / dc;
+      }
+    }
+    tab.bits()[k] |= (lower ? 1u << mifc::VDERIV_LOWER_BIT : 0u) | (upper ? 1u << mifc::VDERIV_UPPER_BIT : 0u) | (fold ? 1u << mifc::VDERIV_FOLD_BIT : 0u);
+  }
+}
+
+int BandPlan::place(mifc_ctx* c, Staging& st, const LevelBatchCall& a, size_t budget, int halo_rows)
 {
   if (a.memkind != MIFC_MEM_HOST) {
     uintptr_t all = 0;
@@ -145,16 +179,21 @@ int BandPlan::place(mifc_ctx* c, Staging& st, const LevelBatchCall& a, size_t bu
   size_t planes = 0;
   for (int i = 0; i < n_; ++i)
     planes += g_[i].planes;
-  const Band band = plan_band(budget, planes, (size_t)a.nx, (size_t)a.ny);
-  float* d = static_cast<float*>(st.scratch(planes * band.S * sizeof(float)));
+  const size_t nx = (size_t)a.nx, ny = (size_t)a.ny, around = 2 * (size_t)halo_rows;
+  size_t staged = plan_band(budget, planes, nx, ny);
+  if (around != 0)
+    staged = std::min(ny, std::max(around + 1, staged));
+  const size_t S = align_up(staged * nx, 64);
+  float* d = static_cast<float*>(st.scratch(planes * S * sizeof(float)));
   if (!st.ok())
     return 0;
   for (int i = 0; i < n_; ++i) {
     g_[i].dev = g_[i].planes ? d : nullptr;
-    d += g_[i].planes * band.S;
+    d += g_[i].planes * S;
   }
-  rows_ = band.rows;
-  stride = (long)band.S;
+  own_ = (int)(staged >= ny ? ny : staged - around);
+  halo_ = halo_rows;
+  stride = (long)S;
   vec4 = 1;
   return 1;
 }

@@ -13,23 +13,19 @@
 // ring cells sit in the lane of their interior neighbour (V = 4) or are stored by it (V = 1): the ring is a copy
 // (fillEdges).  No address leaves the planes: a halo index is clamped into the row, lanes past the tile's end walk the
 // tile's first cells and neither store nor count.
-// The vertical derivatives are the double r of mifc_vderiv_* before its rounding, by the same two bodies: where every
+// The vertical derivatives are the double r of mifc_vderiv_* before its rounding, from the one statement of its rules
+// that vderiv_kernel uses too (mifc_vderiv_cell.h; the coordinate of a level: mifc_column_walk.h), by the same two bodies: where every
 // interior cell of the wave has both sides for all three fields and eight defined neighbours -- one ballot -- the fast
 // body runs without a select, the general body does the rest.  Undefined interior cells are counted per level by ballot
 // into one LDS word per tile buffer and leave the workgroup as one atomic per level that has something to count (DESIGN.md
 // 4.8, 4.17c): no limit on nlev follows.
-#include "mifc_column_walk.h"
-#include "mifc_device.h"
 #include "mifc_kernels.h"
-
-#include <type_traits>
+#include "mifc_vderiv_cell.h"
 
 namespace mifc {
 
 namespace {
 
-const unsigned int SIDE_LOWER = 1u, SIDE_UPPER = 2u, SIDE_BOTH = 3u;
-const unsigned int CELL_LOWER = 1u, CELL_UPPER = 2u, CELL_CENTRE = 4u, CELL_FOLD = 8u;
 constexpr int LX = PVORT_LANES_X, TY = PVORT_TILE_ROWS;
 constexpr int FU = 0, FV = 1, FT = 2;
 const unsigned int LANE_COUNTED = 4 /* bits 0 .. 3: the cell is inside */, LANE_ACTIVE = 1u << 8, LANE_STORE_SELF = 1u << 9, LANE_STORE_FIRST = 1u << 10, LANE_STORE_LAST = 1u << 11,
@@ -139,7 +135,6 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
   };
 
   // what does not depend on the level: the map ratios and the Coriolis parameter of the lane's cells, ps
-  const float nan = __int_as_float(0x7fc00000);
   float xm[V], ym[V], fc[V], ps[V];
   walk_load<V>(xm, P.xmapr + own_off);
   walk_load<V>(ym, P.ymapr + own_off);
@@ -151,40 +146,8 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
     walk_load<V>(fc, P.fcoriolis + own_off);
   if constexpr (KIND == VDERIV_HYBRID) {
     walk_load<V>(ps, P.coord + own_off);
-#pragma unroll
-    for (int c = 0; c < V; ++c)
-      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan; // a coordinate that is not usable is carried as NaN (rule 1)
+    walk_usable_ps<V>(ps, P.ps_all != 0, undef); // a coordinate that is not usable is carried as NaN (rule 1)
   }
-  auto coordinate = [&](const Level& L, int k, unsigned int bits, float (&cc)[V]) {
-    if constexpr (KIND == VDERIV_HYBRID) {
-      const float a = ab[k], b = ab[nlev + k];
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
-        cc[c] = a + prod;
-      }
-    } else if constexpr (KIND == VDERIV_FIELD) {
-      const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = (all || L.c[c] != undef) ? L.c[c] : nan;
-    } else {
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = 0.f; // not used: the table says which sides exist
-    }
-  };
-  // bit f of the cell's word = x_f passes is_defined
-  auto defined = [&](const Level& L, unsigned int bits, unsigned int (&df)[V]) {
-#pragma unroll
-    for (int c = 0; c < V; ++c) {
-      unsigned int w = 0;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-        w |= (((bits >> f) & 1u) != 0 || is_def(L.x[f][c], undef)) ? 1u << f : 0u;
-      df[c] = walk_here_v(w);
-    }
-  };
 
   // stores level k; a row of the output at `row` (a grid row)
   auto store_row = [&](const float (&res)[V], int k, int row, unsigned int lane) {
@@ -203,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
   };
 
   // Output level k from the levels k - 1 (lo), k (cur) and k + 1 (hi), their coordinates cp, cc, cn and the words of
-  // defined() dfp, dfk, dfn; the halo piece h of level k.
+  // vderiv_defined dfp, dfk, dfn; the halo piece h of level k.
   auto level = [&](const Level& lo, const Level& cur, const Level& hi, const float (&h)[V], const float (&cp)[V], const float (&cc)[V],
                    const float (&cn)[V], const unsigned int (&dfp)[V], const unsigned int (&dfk)[V], const unsigned int (&dfn)[V],
                    unsigned int bits_k, int k) {
@@ -248,61 +211,18 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
       nb_ok = walk_here_v(nb_ok);
     }
 
-    // rules 1 and 3 of mifc_vderiv_* for the coordinate, then the sides of every field, as in vderiv_kernel
+    // rules 1 and 3 of mifc_vderiv_* for the coordinate, then the sides of every field (mifc_vderiv_cell.h)
     const bool weighted = walk_here(method) != 0;
     unsigned int cm[V];
     double h1[V], h2[V], den[V];
-#pragma unroll
-    for (int c = 0; c < V; ++c) {
-      if constexpr (KIND == VDERIV_LEVELS) {
-        cm[c] = ((bits_k >> VDERIV_LOWER_BIT) & 1u) * CELL_LOWER | ((bits_k >> VDERIV_UPPER_BIT) & 1u) * CELL_UPPER | CELL_CENTRE |
-                ((bits_k >> VDERIV_FOLD_BIT) & 1u) * CELL_FOLD;
-        h1[c] = h2[c] = den[c] = 0.0;
-      } else {
-        const double dm = (double)cp[c], d0 = (double)cc[c], dp = (double)cn[c];
-        h1[c] = d0 - dm;
-        h2[c] = dp - d0;
-        const double s = h1[c] + h2[c], dc = dp - dm;
-        den[c] = weighted ? s : dc;
-        cm[c] = ((cp[c] == cp[c] && cp[c] != cc[c]) ? CELL_LOWER : 0u) | // (no level k - 1: cp is NaN)
-                ((cn[c] == cn[c] && cn[c] != cc[c]) ? CELL_UPPER : 0u) | (cc[c] == cc[c] ? CELL_CENTRE : 0u) | (den[c] == 0.0 ? CELL_FOLD : 0u);
-        cm[c] = walk_here_v(cm[c]);
-      }
-    }
+    vderiv_cell_mask<KIND, V>(cm, h1, h2, den, cp, cc, cn, bits_k, weighted);
     unsigned int cls[V];
     unsigned int every = SIDE_BOTH, any = 0;
 #pragma unroll
-    for (int c = 0; c < V; ++c) {
-      cls[c] = 0;
-      const bool in = ((lane >> c) & 1u) != 0;
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        const unsigned int okbits = ((dfp[c] >> f) & 1u) * CELL_LOWER | ((dfn[c] >> f) & 1u) * CELL_UPPER | ((dfk[c] >> f) & 1u) * CELL_CENTRE | CELL_FOLD;
-        const unsigned int tt = cm[c] & okbits;
-        unsigned int s = tt & SIDE_BOTH;
-        s = ((tt & CELL_CENTRE) != 0 && tt != (SIDE_BOTH | CELL_CENTRE | CELL_FOLD)) ? s : 0u;
-        s = in ? s : SIDE_BOTH; // (a cell that is not stored as itself decides nothing)
-        cls[c] |= s << (2 * f);
-        any |= (1u << s) >> 1;
-        every &= s;
-      }
-    }
+    for (int c = 0; c < V; ++c)
+      cls[c] = vderiv_classify<NF>(every, any, cm[c], dfp[c], dfk[c], dfn[c], ((lane >> c) & 1u) != 0);
     const bool good = every == SIDE_BOTH && nb_ok == (1u << V) - 1u;
 
-    // the two-sided weights of rule 4 of mifc_vderiv_* for one cell (CENTRED: wa = w; WEIGHTED: wa = w1, wb = w2)
-    auto both_weights = [&](int c, double& wa, double& wb) {
-      if constexpr (KIND == VDERIV_LEVELS) {
-        wa = lev_w[4 * k + 2];
-        wb = lev_w[4 * k + 3];
-      } else if (weighted) {
-        const double p1 = h1[c] * den[c], p2 = h2[c] * den[c];
-        wa = h2[c] / p1;
-        wb = h1[c] / p2;
-      } else {
-        wa = 1.0 / den[c];
-        wb = 0.0;
-      }
-    };
     // rules 3 to 5 of this entry for one cell from its derivatives
     const double scale = P.scale;
     auto product = [&](int c, double Du, double Dv, double Dt) -> float {
@@ -322,15 +242,10 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
 #pragma unroll
       for (int c = 0; c < V; ++c) {
         double wa, wb, D[NF];
-        both_weights(c, wa, wb);
+        vderiv_both_weights<KIND>(wa, wb, h1[c], h2[c], den[c], weighted, lev_w, k);
 #pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          const double xmm = (double)lo.x[f][c], x0d = (double)cur.x[f][c], xp = (double)hi.x[f][c];
-          const double d1 = x0d - xmm, d2 = xp - x0d, d = xp - xmm;
-          const double t1 = d1 * wa, t2 = d2 * wb;
-          const double sum = t1 + t2, centred = d * wa;
-          D[f] = weighted ? sum : centred;
-        }
+        for (int f = 0; f < NF; ++f)
+          D[f] = vderiv_both(lo.x[f][c], cur.x[f][c], hi.x[f][c], wa, wb, weighted);
         res[c] = product(c, D[FU], D[FV], D[FT]);
       }
     } else {
@@ -342,31 +257,15 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
 #pragma unroll
       for (int c = 0; c < V; ++c) {
         double wl = 0.0, wh = 0.0, wa = 0.0, wb = 0.0, D[NF];
-        if (need_lower) {
-          if constexpr (KIND == VDERIV_LEVELS)
-            wl = lev_w[4 * k];
-          else
-            wl = 1.0 / h1[c];
-        }
-        if (need_upper) {
-          if constexpr (KIND == VDERIV_LEVELS)
-            wh = lev_w[4 * k + 1];
-          else
-            wh = 1.0 / h2[c];
-        }
+        if (need_lower)
+          wl = vderiv_one_weight<KIND, false>(h1[c], lev_w, k);
+        if (need_upper)
+          wh = vderiv_one_weight<KIND, true>(h2[c], lev_w, k);
         if (need_both)
-          both_weights(c, wa, wb);
+          vderiv_both_weights<KIND>(wa, wb, h1[c], h2[c], den[c], weighted, lev_w, k);
 #pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          const unsigned int s = (cls[c] >> (2 * f)) & 3u;
-          const double xmm = (double)lo.x[f][c], x0d = (double)cur.x[f][c], xp = (double)hi.x[f][c];
-          const double d1 = x0d - xmm, d2 = xp - x0d, d = xp - xmm;
-          const double one_lower = d1 * wl, one_upper = d2 * wh;
-          const double t1 = d1 * wa, t2 = d2 * wb;
-          const double sum = t1 + t2, centred = d * wa;
-          const double both = weighted ? sum : centred;
-          D[f] = s == SIDE_BOTH ? both : (s == SIDE_LOWER ? one_lower : one_upper);
-        }
+        for (int f = 0; f < NF; ++f)
+          D[f] = vderiv_sided((cls[c] >> (2 * f)) & 3u, lo.x[f][c], cur.x[f][c], hi.x[f][c], wl, wh, wa, wb, weighted);
         const float r = product(c, D[FU], D[FV], D[FT]);
         const bool bad = ((cls[c] & 3u) == 0 || ((cls[c] >> 2) & 3u) == 0 || ((cls[c] >> 4) & 3u) == 0 || ((nb_ok >> c) & 1u) == 0);
         res[c] = bad ? undef : r;
@@ -389,6 +288,7 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
       store_row(res, k, P.ny - 1, lane);
   };
 
+  const float nan = __int_as_float(0x7fc00000);
   Level L[R], prev;
   float H[R][V];
 #pragma unroll
@@ -412,8 +312,8 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
     cp[c] = nan;
     dfp[c] = 0;
   }
-  coordinate(L[0], 0, bits_k, cc);
-  defined(L[0], bits_k, dfk);
+  walk_coordinate<KIND, V>(cc, L[0].c, ps, ab, nlev, 0, bits_k, undef);
+  vderiv_defined<NF, V>(dfk, L[0], bits_k, undef);
 
   for (int k0 = 0; k0 < nlev; k0 += R) {
 #pragma unroll
@@ -425,12 +325,12 @@ __global__ __launch_bounds__(256, 2) void pvort_kernel(const PvortParams P)
         const bool has_next = k + 1 < nlev;
         const unsigned int bits_n = lev_bits[has_next ? k + 1 : k];
         float cn[V];
-        coordinate(nxt, has_next ? k + 1 : k, bits_n, cn);
+        walk_coordinate<KIND, V>(cn, nxt.c, ps, ab, nlev, has_next ? k + 1 : k, bits_n, undef);
 #pragma unroll
         for (int c = 0; c < V; ++c)
           cn[c] = has_next ? cn[c] : nan;
         unsigned int dfn[V];
-        defined(nxt, bits_n, dfn); // (no level k + 1: cn is NaN)
+        vderiv_defined<NF, V>(dfn, nxt, bits_n, undef); // (no level k + 1: cn is NaN)
         level(prev, cur, nxt, H[d], cp, cc, cn, dfp, dfk, dfn, bits_k, k);
         // level k becomes level k - 1, level k + 1 level k; level k's slot takes level k + 3
         prev = cur;

@@ -14,21 +14,16 @@
 // both / lower only / upper only / undef, computes only the weights that some cell of the wave needs and selects.  With
 // the coordinate given per level (VDERIV_LEVELS) the weights are the same for every cell: the host has divided, they come
 // in through scalar loads.  Undefined cells are counted per level and field by ballot into LDS and leave the workgroup as
-// one atomic per counter that is not zero.
-#include "mifc_column_walk.h"
-#include "mifc_device.h"
+// one atomic per counter that is not zero.  The rules themselves -- the sides, the weights, the
+// derivative of one (field, cell) -- are stated in mifc_vderiv_cell.h, for this kernel and pvort_kernel (mifc_pvort.hip).
 #include "mifc_kernels.h"
+#include "mifc_vderiv_cell.h"
 
 #include <type_traits>
 
 namespace mifc {
 
 namespace {
-
-// what a (field, cell) of a level is, two bits: the sides that take part; 0 = the result is undef
-const unsigned int SIDE_LOWER = 1u, SIDE_UPPER = 2u, SIDE_BOTH = 3u;
-// what the coordinate of a cell allows at a level (SIDE_* in the low bits)
-const unsigned int CELL_LOWER = 1u, CELL_UPPER = 2u, CELL_CENTRE = 4u, CELL_FOLD = 8u;
 
 template <int KIND, int W, int NF, int V>
 __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
@@ -69,47 +64,11 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
   };
 
   // a coordinate that is not usable is carried as NaN (rule 1)
-  const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (KIND == VDERIV_HYBRID) {
     walk_load<V>(ps, lane_of(P.coord + block0));
-#pragma unroll
-    for (int c = 0; c < V; ++c)
-      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan;
+    walk_usable_ps<V>(ps, P.ps_all != 0, undef);
   }
-  auto coordinate = [&](const Level& L, int k, unsigned int bits, float (&cc)[V]) {
-    if constexpr (KIND == VDERIV_HYBRID) {
-      const float a = ab[k], b = ab[nlev + k];
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
-        cc[c] = a + prod;
-      }
-    } else if constexpr (KIND == VDERIV_FIELD) {
-      const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = (all || L.c[c] != undef) ? L.c[c] : nan;
-    } else {
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = 0.f; // not used: the table says which sides exist
-    }
-  };
-
-  // rule 2 for the values of a level as it arrives: bit f of the cell's word = x_f passes is_defined.  Every value is tested
-  // once; as lane masks the tests of the three levels in flight would not fit into the SGPRs
-  auto defined = [&](const Level& L, unsigned int bits, unsigned int (&df)[V]) {
-    const unsigned int all = bits >> f0;
-#pragma unroll
-    for (int c = 0; c < V; ++c) {
-      unsigned int w = 0;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-        w |= (((all >> f) & 1u) != 0 || is_def(L.x[f][c], undef)) ? 1u << f : 0u;
-      df[c] = walk_here_v(w);
-    }
-  };
 
   auto count = [&](int slot, int k, unsigned int n) {
     // (the lane test and the row of the counter computed here, not kept in SGPRs through the walk)
@@ -165,67 +124,24 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
   };
 
   // Output level k from the levels k - 1 (lo), k (cur) and k + 1 (hi) and their coordinates cp, cc, cn.
-  // dfp, dfk, dfn: the words of defined() for the three levels.
+  // dfp, dfk, dfn: the words of vderiv_defined for the three levels.  The rules are those of mifc_vderiv_cell.h.
   auto level = [&](const Level& lo, const Level& cur, const Level& hi, const float (&cp)[V], const float (&cc)[V], const float (&cn)[V],
                    const unsigned int (&dfp)[V], const unsigned int (&dfk)[V], const unsigned int (&dfn)[V], unsigned int bits_k, int k) {
-    // rules 1 and 3 for the coordinate: is c_k usable, does c_k-1 / c_k+1 exist, is it usable and different
-    // per cell in a VGPR (as lane masks these sixteen tests would take more SGPRs than a wave has to spare): CELL_LOWER /
-    // CELL_UPPER = the side's coordinate is usable and differs, CELL_CENTRE = c_k is usable, CELL_FOLD = zero denominator
     const bool weighted = walk_here(method) != 0; // (tested here: as lane masks for the selects it would sit in four SGPRs through the walk)
     unsigned int cm[V];
     double h1[V], h2[V], den[V];
-#pragma unroll
-    for (int c = 0; c < V; ++c) {
-      if constexpr (KIND == VDERIV_LEVELS) {
-        cm[c] = ((bits_k >> VDERIV_LOWER_BIT) & 1u) * CELL_LOWER | ((bits_k >> VDERIV_UPPER_BIT) & 1u) * CELL_UPPER | CELL_CENTRE |
-                ((bits_k >> VDERIV_FOLD_BIT) & 1u) * CELL_FOLD;
-        h1[c] = h2[c] = den[c] = 0.0;
-      } else {
-        const double dm = (double)cp[c], d0 = (double)cc[c], dp = (double)cn[c];
-        h1[c] = d0 - dm;
-        h2[c] = dp - d0;
-        const double s = h1[c] + h2[c], dc = dp - dm;
-        den[c] = weighted ? s : dc;
-        cm[c] = ((cp[c] == cp[c] && cp[c] != cc[c]) ? CELL_LOWER : 0u) | // (no level k - 1: cp is NaN)
-                ((cn[c] == cn[c] && cn[c] != cc[c]) ? CELL_UPPER : 0u) | (cc[c] == cc[c] ? CELL_CENTRE : 0u) | (den[c] == 0.0 ? CELL_FOLD : 0u);
-        cm[c] = walk_here_v(cm[c]);
-      }
-    }
-    // the two-sided weights of rule 4 (CENTRED: wa = w; WEIGHTED: wa = w1, wb = w2)
+    vderiv_cell_mask<KIND, V>(cm, h1, h2, den, cp, cc, cn, bits_k, weighted);
     auto both_weights = [&](double (&wa)[V], double (&wb)[V]) {
 #pragma unroll
-      for (int c = 0; c < V; ++c) {
-        if constexpr (KIND == VDERIV_LEVELS) {
-          wa[c] = lev_w[4 * k + 2];
-          wb[c] = lev_w[4 * k + 3];
-        } else if (weighted) {
-          const double p1 = h1[c] * den[c], p2 = h2[c] * den[c];
-          wa[c] = h2[c] / p1;
-          wb[c] = h1[c] / p2;
-        } else {
-          wa[c] = 1.0 / den[c];
-          wb[c] = 0.0;
-        }
-      }
+      for (int c = 0; c < V; ++c)
+        vderiv_both_weights<KIND>(wa[c], wb[c], h1[c], h2[c], den[c], weighted, lev_w, k);
     };
 
     unsigned int cls[V];
-    unsigned int every = SIDE_BOTH; // the AND of the lane's classes: SIDE_BOTH = all of them are
-    unsigned int any = 0;           // which classes this lane has: bit s - 1 for SIDE_* s
+    unsigned int every = SIDE_BOTH, any = 0;
 #pragma unroll
-    for (int c = 0; c < V; ++c) {
-      cls[c] = 0;
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        const unsigned int okbits = ((dfp[c] >> f) & 1u) * CELL_LOWER | ((dfn[c] >> f) & 1u) * CELL_UPPER | ((dfk[c] >> f) & 1u) * CELL_CENTRE | CELL_FOLD;
-        const unsigned int t = cm[c] & okbits;
-        unsigned int s = t & SIDE_BOTH; // rule 3 (CELL_LOWER, CELL_UPPER are SIDE_LOWER, SIDE_UPPER)
-        s = ((t & CELL_CENTRE) != 0 && t != (SIDE_BOTH | CELL_CENTRE | CELL_FOLD)) ? s : 0u; // rule 2; rule 4's zero denominator
-        cls[c] |= s << (2 * f);
-        any |= (1u << s) >> 1;
-        every &= s;
-      }
-    }
+    for (int c = 0; c < V; ++c)
+      cls[c] = vderiv_classify<NF>(every, any, cm[c], dfp[c], dfk[c], dfn[c]);
     const bool good = every == SIDE_BOTH;
 
     float res[NF][V];
@@ -237,22 +153,14 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-          for (int c = 0; c < V; ++c) {
-            const double xm = (double)lo.x[f][c], x0 = (double)cur.x[f][c], xp = (double)hi.x[f][c];
-            const double d1 = x0 - xm, d2 = xp - x0;
-            const double t1 = d1 * wa[c], t2 = d2 * wb[c];
-            const double r = t1 + t2;
-            res[f][c] = (float)r;
-          }
+          for (int c = 0; c < V; ++c)
+            res[f][c] = (float)vderiv_both(lo.x[f][c], cur.x[f][c], hi.x[f][c], wa[c], wb[c], true);
       } else {
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-          for (int c = 0; c < V; ++c) {
-            const double d = (double)hi.x[f][c] - (double)lo.x[f][c];
-            const double r = d * wa[c];
-            res[f][c] = (float)r;
-          }
+          for (int c = 0; c < V; ++c)
+            res[f][c] = (float)vderiv_both(lo.x[f][c], cur.x[f][c], hi.x[f][c], wa[c], wb[c], false);
       }
       emit(std::true_type(), res, cls, k);
       return;
@@ -265,21 +173,13 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
       wl[c] = wh[c] = wa[c] = wb[c] = 0.0;
     if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_LOWER - 1))) != 0) != 0) {
 #pragma unroll
-      for (int c = 0; c < V; ++c) {
-        if constexpr (KIND == VDERIV_LEVELS)
-          wl[c] = lev_w[4 * k];
-        else
-          wl[c] = 1.0 / h1[c];
-      }
+      for (int c = 0; c < V; ++c)
+        wl[c] = vderiv_one_weight<KIND, false>(h1[c], lev_w, k);
     }
     if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_UPPER - 1))) != 0) != 0) {
 #pragma unroll
-      for (int c = 0; c < V; ++c) {
-        if constexpr (KIND == VDERIV_LEVELS)
-          wh[c] = lev_w[4 * k + 1];
-        else
-          wh[c] = 1.0 / h2[c];
-      }
+      for (int c = 0; c < V; ++c)
+        wh[c] = vderiv_one_weight<KIND, true>(h2[c], lev_w, k);
     }
     if (__builtin_amdgcn_ballot_w64((any & (1u << (SIDE_BOTH - 1))) != 0) != 0)
       both_weights(wa, wb);
@@ -288,18 +188,13 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
 #pragma unroll
       for (int c = 0; c < V; ++c) {
         const unsigned int s = (cls[c] >> (2 * f)) & 3u;
-        const double xm = (double)lo.x[f][c], x0 = (double)cur.x[f][c], xp = (double)hi.x[f][c];
-        const double d1 = x0 - xm, d2 = xp - x0, d = xp - xm;
-        const double one_lower = d1 * wl[c], one_upper = d2 * wh[c]; // rule 5
-        const double t1 = d1 * wa[c], t2 = d2 * wb[c];
-        const double sum = t1 + t2, centred = d * wa[c];
-        const double both = weighted ? sum : centred;
-        const double r = s == SIDE_BOTH ? both : (s == SIDE_LOWER ? one_lower : one_upper);
+        const double r = vderiv_sided(s, lo.x[f][c], cur.x[f][c], hi.x[f][c], wl[c], wh[c], wa[c], wb[c], weighted);
         res[f][c] = s == 0 ? undef : (float)r;
       }
     emit(std::false_type(), res, cls, k);
   };
 
+  const float nan = __int_as_float(0x7fc00000);
   Level L[R], prev;
 #pragma unroll
   for (int c = 0; c < V; ++c) {
@@ -321,8 +216,8 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
     cp[c] = nan;
     dfp[c] = 0;
   }
-  coordinate(L[0], 0, bits_k, cc);
-  defined(L[0], bits_k, dfk);
+  walk_coordinate<KIND, V>(cc, L[0].c, ps, ab, nlev, 0, bits_k, undef);
+  vderiv_defined<NF, V>(dfk, L[0], bits_k >> f0, undef);
 
   for (int k0 = 0; k0 < nlev; k0 += R) {
 #pragma unroll
@@ -334,12 +229,12 @@ __global__ __launch_bounds__(256, 2) void vderiv_kernel(const VderivParams P)
         const bool has_next = k + 1 < nlev;
         const unsigned int bits_n = lev_bits[has_next ? k + 1 : k];
         float cn[V];
-        coordinate(nx, has_next ? k + 1 : k, bits_n, cn);
+        walk_coordinate<KIND, V>(cn, nx.c, ps, ab, nlev, has_next ? k + 1 : k, bits_n, undef);
 #pragma unroll
         for (int c = 0; c < V; ++c)
           cn[c] = has_next ? cn[c] : nan;
         unsigned int dfn[V];
-        defined(nx, bits_n, dfn); // (no level k + 1: cn is NaN)
+        vderiv_defined<NF, V>(dfn, nx, bits_n >> f0, undef); // (no level k + 1: cn is NaN)
         level(prev, cur, nx, cp, cc, cn, dfp, dfk, dfn, bits_k, k);
         // level k becomes level k - 1, level k + 1 level k; level k's slot takes level k + 3
         prev = cur;

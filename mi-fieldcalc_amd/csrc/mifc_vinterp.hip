@@ -82,28 +82,13 @@ __global__ __launch_bounds__(256) void vinterp_kernel(const VinterpParams P)
 
   // An undefined coordinate is carried as NaN: a NaN coordinate never brackets anyway (it fails both comparisons), so
   // "both ends defined" is one ordered compare of the pair, and no flag per cell has to live through the walk.
-  const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (HYBRID) {
     walk_load<V>(ps, P.coord + at);
-#pragma unroll
-    for (int c = 0; c < V; ++c)
-      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan; // an undefined ps: every level of the cell undefined
+    walk_usable_ps<V>(ps, P.ps_all != 0, undef);
   }
   auto coordinate = [&](const WalkLevel<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
-    if constexpr (HYBRID) {
-      const float a = ab[k], b = ab[nlev + k];
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
-        cc[c] = a + prod;
-      }
-    } else {
-      const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = (all || L.c[c] != undef) ? L.c[c] : nan;
-    }
+    walk_coordinate<HYBRID ? VDERIV_HYBRID : VDERIV_FIELD, V>(cc, L.c, ps, ab, nlev, k, bits, undef);
   };
 
   // level k lives in slot k % 3: at the pair (k, k + 1) the third slot holds level k + 2, already on its way, and the

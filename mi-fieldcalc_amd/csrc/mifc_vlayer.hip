@@ -151,28 +151,17 @@ __global__ __launch_bounds__(256, 2) void vlayer_kernel(const VlayerParams P)
   };
 
   // an undefined coordinate is carried as NaN: it makes the cell undefined like a NaN that came in as a value (rule 1)
-  const float nan = __int_as_float(0x7fc00000);
   float ps[V];
   if constexpr (HYBRID) {
     walk_load<V>(ps, lane_of(P.coord + block0));
+    // (walk_usable_ps, written out: through the helper the hybrid instances with four cells per lane come out of the
+    // register allocator 3 to 5 % slower on two or four fields, profiles/README.md)
 #pragma unroll
     for (int c = 0; c < V; ++c)
-      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : nan;
+      ps[c] = (P.ps_all != 0 || ps[c] != undef) ? ps[c] : __int_as_float(0x7fc00000);
   }
   auto coordinate = [&](const WalkLevel<NF, V>& L, int k, unsigned int bits, float (&cc)[V]) {
-    if constexpr (HYBRID) {
-      const float a = ab[k], b = ab[nlev + k];
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float prod = b * ps[c]; // p_hlevel, FieldCalculations.cc:303: the product rounded, then the sum
-        cc[c] = a + prod;
-      }
-    } else {
-      const bool all = ((bits >> VINTERP_COORD_BIT) & 1u) != 0;
-#pragma unroll
-      for (int c = 0; c < V; ++c)
-        cc[c] = (all || L.c[c] != undef) ? L.c[c] : nan;
-    }
+    walk_coordinate<HYBRID ? VDERIV_HYBRID : VDERIV_FIELD, V>(cc, L.c, ps, ab, nlev, k, bits, undef);
   };
 
   WalkLevel<NF, V> L[R];

@@ -244,6 +244,46 @@ def test_host_bands(gpu_ctx, mifc_env):
     compare(got, exp, fd, efd, "one band")
 
 
+def bands_of(nlev, ny, nx, coord_planes, n_map, mib=1):
+    """The bands of a host call from the rule of the level-batch driver with a halo of one row, restated: the rows that fit
+    the budget (each plane padded to 64 floats, one row at least), three staged at least and ny at most, two of the staged
+    rows are neighbours unless one band holds every row."""
+    planes, budget = 4 * nlev + coord_planes + n_map, mib << 20
+    rows = max(1, min(ny, budget // (planes * nx * 4)))
+    while rows > 1 and planes * (-(-rows * nx // 64) * 64) * 4 > budget:
+        rows -= 1
+    staged = min(ny, max(3, rows))
+    own = ny if staged >= ny else staged - 2
+    return -(-ny // own)
+
+
+@pytest.mark.parametrize("ny,nx,kind,fcor", [(3, 10924, "hybrid", True), (5, 10924, "hybrid", True), (5, 10926, "field", False), (6, 5464, "levels", True)],
+                         ids=["ny3", "ny5_one_row_owned", "ny5_dword_form", "ny6_two_rows_owned"])
+def test_host_bands_of_few_rows(gpu_ctx, mifc_env, ny, nx, kind, fcor):
+    """MIFC_PVORT_CHUNK_MIB=1, 12 or 11 planes: a row of 10924 floats in 12 planes is half a MiB, fewer than three rows fit, so
+    three are staged and one is owned.  ny = 5: five bands; rows 0 and 4 are owned by bands that compute row 1 and row 3 for them
+    and do not count them, rows 1 and 3 by bands of their own.  ny = 3: the three staged rows are all there are, so one band
+    holds every row whatever the budget (the rule above; there is no way to own one row of three).  nx = 10926: no multiple
+    of four, one cell per lane with a halo.  ny = 6 of 5464: four staged, two owned, three bands.  Holes on every row; the
+    host call against the restatement and against the one-launch device call, bit for bit, flags included."""
+    mifc_env("MIFC_PVORT_CHUNK_MIB", 1)
+    nlev = 2
+    bands = bands_of(nlev, ny, nx, {"hybrid": 1, "field": nlev, "levels": 0}[kind], 3 if fcor else 2)
+    assert bands == {3: 1, 5: 5, 6: 3}[ny]
+    c = {k: a.copy() for k, a in pv.pv_case(nlev, ny, nx, seed=17, frac=0.001).items()}
+    rng = np.random.default_rng(4)
+    for r in range(ny):
+        for a in (c["u"], c["v"], c["th"]):
+            a[rng.integers(0, nlev), r, rng.integers(0, nx, 5)] = U
+    for given, method in METHODS:
+        exp, efd = expected(kind, c, method, fcor)
+        got, fd = run(gpu_ctx, kind, c, given, False, fcor, form={"launches": bands, "bands": bands})
+        compare(got, exp, fd, efd, (ny, nx, kind, method, "bands"))
+        dev, dfd = run(gpu_ctx, kind, c, given, True, fcor, pad=64 if nx % 4 == 0 else 65)
+        compare(dev, got, dfd, fd, (ny, nx, kind, method, "device"))
+        assert (efd == S_).all()
+
+
 def test_identity_a_absvort_on_the_device(gpu_ctx):
     import torch
 

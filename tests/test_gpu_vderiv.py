@@ -212,6 +212,13 @@ def test_host_call_in_several_bands(gpu_ctx, mifc_env):
     all_kinds(gpu_ctx, case, METHODS[0], False, magnitude="also", label="bands")
     all_kinds(gpu_ctx, case, METHODS[1], False, magnitude="only", label="bands")
     check(gpu_ctx, "field", case[0], case[3], METHODS[1], False, label="bands")
+    # the five bands against the one-launch device call itself, bit for bit, flags included
+    fields, ps, ab, coord, levs = case
+    for kind, c in (("hybrid", ps), ("field", coord), ("levels", levs)):
+        host = run(gpu_ctx, kind, fields, c, "weighted", False, ab=ab, magnitude="also")
+        dev = run(gpu_ctx, kind, fields, c, "weighted", True, ab=ab, magnitude="also")
+        for j in (0, 2):
+            compare(host[j], dev[j], host[j + 1], dev[j + 1], ("bands against the device call", kind, j))
 
 
 def test_host_band_of_one_row_that_exceeds_the_budget(gpu_ctx, mifc_env):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Prints VGPRs / SGPRs / LDS bytes / scratch bytes of every gfx950 kernel in a hipcc object file (no GPU needed).
+# Prints VGPRs / SGPRs / LDS bytes / scratch bytes / SGPR and VGPR spill counts of every gfx950 kernel in a hipcc object file (no GPU needed).
 # Usage: tools/kernel_resources.sh mi-fieldcalc_amd/csrc/mifc_stencil_split.o [name filter]
 set -e
 LLVM=/opt/rocm/lib/llvm/bin
@@ -22,9 +22,9 @@ for blk in txt.split("- .agpr_count")[1:]:
         pass
     name = name.replace("mifc::(anonymous namespace)::", "").replace("(mifc::SRowsParams)", "").replace("(mifc::(anonymous namespace)::RowsParams)", "")
     if flt in name:
-        rows.append((name, g("vgpr_count"), g("sgpr_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size")))
-print("%-70s %5s %5s %7s %7s" % ("kernel", "vgpr", "sgpr", "lds", "scratch"))
+        rows.append((name, g("vgpr_count"), g("sgpr_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size"), g("sgpr_spill_count"), g("vgpr_spill_count")))
+print("%-70s %5s %5s %7s %7s %7s %7s" % ("kernel", "vgpr", "sgpr", "lds", "scratch", "s_spill", "v_spill"))
 for r in sorted(rows):
-    print("%-70s %5s %5s %7s %7s" % r)
+    print("%-70s %5s %5s %7s %7s %7s %7s" % r)
 ' "${2:-}"
 rm -rf "$T"
