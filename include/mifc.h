@@ -899,6 +899,70 @@ int mifc_hstats_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* con
                        int* fdefined_mean, float undef, int memkind);
 const char* mifc_last_hstats_form(void);
 
+/* ---- EXTENSION: level batches regridded by a sparse weight table (conservative remapping, region averages) ----
+ * Not a miutil::fieldcalc function.  mifc_hinterp_levels samples points, so it cannot conserve a quantity: precipitation,
+ * fluxes, cloud cover and land or ice fractions, and any field taken to a coarser grid, are regridded with area-overlap
+ * weights, which every regridding tool (ESMF/SCRIP, CDO, xESMF) delivers as a sparse weight table -- one row of
+ * (source cell, weight) entries per destination cell, computed once per grid pair and applied at every time step.  The
+ * same table form carries first- and second-order conservative remaps, patch recovery, nearest-neighbour remaps, averages
+ * over catchments or regions and any other linear horizontal operator.  The result is again a level batch
+ * (nlev, ndst_y, ndst_x), which every vertical entry and mifc_hstats_levels accept unchanged.
+ *
+ * Table.  A table has ndst rows over nsrc = nx * ny source cells, in CSR form: rowptr is int[ndst + 1], col is int[nnz],
+ * the flat index j * nx + i, w is float[nnz].  The entries of a row may come in any order and may repeat a column.  The
+ * given order is part of the definition.
+ * Sums.  Per destination d, field f and level k, entries e = rowptr[d] .. rowptr[d + 1] - 1 in that order:
+ *   1. x_e = fields[f][k][col[e]] is defined iff is_defined(fdefined_in[f * nlev + k] == ALL_DEFINED, x_e, undef).  This is
+ *      rule 3 of mifc_hinterp_levels: a stored undef under ALL_DEFINED is a value.
+ *   2. Sums are in double, sequential, each starting from +0.0.  Every operation is rounded on its own, with no
+ *      contraction.  S = S + (double)w_e * (double)x_e over the defined entries; the product is exact.
+ *      Wdef = Wdef + (double)w_e over the defined entries.  Wall is the same sum over all entries; it is a property of
+ *      the row, computed once when the plan is made.  nbad is the number of undefined entries.
+ *   3. MIFC_HREMAP_STRICT = 0: the result is undef if the row is empty or nbad > 0, else (float)S.
+ *   4. MIFC_HREMAP_RENORM = 1, with min_frac a double in [0, 1]: an empty row gives undef; nbad == 0 gives (float)S, the
+ *      same bits as STRICT; otherwise the result is undef if every entry is undefined, or Wdef == 0.0, or
+ *      !(fabs(Wdef) >= min_frac * fabs(Wall)); otherwise the result is (float)((S / Wdef) * Wall).  RENORM is meant for
+ *      non-negative weights.
+ *   5. fdefined_out[f * nlev + k] = checkDefined(destinations left undef, ndst).  A computed result is never counted,
+ *      whatever its value.
+ *   6. Consequences: a one-entry row of weight 1 returns the source value bit for bit, except that -0.0 comes back as
+ *      +0.0; a NaN under ALL_DEFINED makes the result NaN; there is no tolerance anywhere.
+ * (Restated in numpy in tests/hremap_restate.py.)
+ *
+ * Plan.  mifc_hremap_plan_create is off the hot path: it brings the three arrays to the host whatever their memory kind
+ * (memkind says where all three live), then validates them and converts them.  The plan owns its device copy; the caller
+ * may free or overwrite its arrays afterwards.  A later kernel reads only memory the library itself validated, so no
+ * caller data can send a lane outside [0, nsrc).  Creation is refused with NULL and a reason in mifc_last_error() for:
+ * nsrc < 1 or ndst < 1; rowptr[0] != 0, or a decreasing rowptr; nnz = rowptr[ndst] negative; a col outside [0, nsrc); a
+ * weight that is NaN or infinite; a null pointer; a bad memkind; an open graph capture.  nnz == 0 is legal: every
+ * destination is undef (col and w are not read then and may be NULL).  The device layout is sliced ELL with slices of 64 destinations, padded to the longest row of
+ * each slice: one very long row makes its 63 neighbours as long.  mifc_hremap_plan_info gives nnz, the
+ * longest row and the number of empty rows (any of the three pointers may be NULL).  A plan belongs to its context, is
+ * destroyed before it, and may be used by any number of calls; mifc_hremap_plan_destroy(NULL) does nothing.
+ *
+ * Entry.  `fields`, `fdefined_in`, nfields (1..8), undef, memkind and pointer alignment are as for mifc_hinterp_levels;
+ * fres[f] is [nlev][ndst]; `fdefined_out` a HOST int[nfields * nlev].  Refused calls return 0, write nothing and give the
+ * reason in mifc_last_error().  They are: a null plan, or a plan of another context; nx * ny != nsrc of the plan;
+ * nlev < 1; nfields outside 1..8; an unknown mode; min_frac NaN or outside [0, 1] (it is ignored but still checked under
+ * STRICT); a required null pointer; an output that overlaps a field or another output by byte range; a bad memkind; an
+ * open graph capture.
+ * Device memory is used where it is, with one synchronisation at the end.  Host memory works at any size: whole levels
+ * are staged per chunk, MIFC_HREMAP_CHUNK_MIB of device memory (default 256) but never less than one level.
+ * Not offered: a wave-per-row form for very long rows, for which mifc_hstats_levels with a weight plane remains the tool;
+ * transposed application; double weights.
+ * mifc_last_hremap_form: the launch shape of the calling thread's last mifc_hremap_levels call, a diagnostic for tests:
+ * "mode=strict|renorm nf=<fields per launch> tested=0|1 blocks=<grid.x> level_chunks=<grid.y> chunk=<levels per chunk>
+ * width=<largest slice width> launches=<n>"; "" before the first call. */
+enum { MIFC_HREMAP_STRICT = 0, MIFC_HREMAP_RENORM = 1 };
+typedef struct mifc_hremap_plan mifc_hremap_plan;
+mifc_hremap_plan* mifc_hremap_plan_create(mifc_ctx* ctx, int nsrc, int ndst, const int* rowptr, const int* col, const float* w, int memkind);
+void mifc_hremap_plan_destroy(mifc_hremap_plan* plan);
+int mifc_hremap_plan_info(const mifc_hremap_plan* plan, long long* nnz, int* max_row, int* empty_rows);
+int mifc_hremap_levels(mifc_ctx* ctx, const mifc_hremap_plan* plan, int nx, int ny, int nlev, const float* const* fields,
+                       const int* fdefined_in, int nfields, int mode, double min_frac,
+                       float* const* fres, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_hremap_form(void);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

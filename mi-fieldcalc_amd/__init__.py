@@ -62,6 +62,10 @@ class Context(_ReferenceOps, _LevelBatchOps, _BatchedOps):
 
     def close(self):
         if getattr(self, "_ctx", None):
+            for ref in self.__dict__.pop("_plans", ()):  # handles that belong to this context go first (hremap.Plan)
+                plan = ref()
+                if plan is not None:
+                    plan.close()
             self._lib.mifc_destroy(self._ctx)
             self._ctx = None
 

@@ -162,6 +162,12 @@ SIGNATURES = {
     # EXTENSION: horizontal statistics of level batches (fields, minus, mean: host tables of pointers; pivot, box: host arrays; stats: double)
     "mifc_hstats_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "p", "i", "pi", "i", "i", "p", "p", "pi", "f", "i"]),
     "mifc_last_hstats_form": ("s", []),
+    # EXTENSION: level batches regridded by a sparse weight table (the plan: rowptr, col, w where memkind says; nnz: long long*)
+    "mifc_hremap_plan_create": ("p", ["ctx", "i", "i", "p", "p", "p", "i"]),
+    "mifc_hremap_plan_destroy": (None, ["p"]),
+    "mifc_hremap_plan_info": ("i", ["p", "p", "pi", "pi"]),
+    "mifc_hremap_levels": ("i", ["ctx", "p", "i", "i", "i", "p", "pi", "i", "i", "d", "p", "pi", "f", "i"]),
+    "mifc_last_hremap_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

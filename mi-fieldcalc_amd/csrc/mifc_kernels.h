@@ -594,6 +594,62 @@ struct HinterpRotateParams : HinterpParams
 };
 hipError_t launch_hinterp_rotate(const HinterpRotateParams& prm, hipStream_t stream);
 
+// ------------------------------------ level batches regridded by a weight table (mifc_hremap.hip), EXTENSION
+// One launch applies a plan's table (the sliced-ELL layout of mifc_hremap_plan.h, on the device) to `nlev` levels of up to
+// hremap_pass_fields(tested) fields: a sparse gather with a variable number of terms per output.  A lane owns one destination, a wave one
+// slice of 64, a workgroup four slices and the levels [blockIdx.y * chunk, + chunk) of the launch, a register block of
+// them (hremap_levels()) at a time with the sums in registers: a lane reads its (col, w) pair once per trip and uses it for those levels and every
+// field of the launch.  Level k of field f lies at fields[f] + k * in_stride ([nsrc]) and is written to
+// out[f] + k * out_stride ([ndst]).  The launch's level k is the call's level lev0 + k, its field f the call's f0 + f:
+// lev_bits[lev0 + k] bit f0 + f says the input is ALL_DEFINED there, destinations with a row that are left undef are
+// counted in n_undefined[(f0 + f) * call_nlev + lev0 + k]; empty rows are the plan's and are added by the caller.
+// A tested launch takes HREMAP_PASS_TESTED fields: with Wdef, nbad and the lane masks of the tests three or four fields
+// by four levels do not fit the scalar registers (the register table).  The register block is
+// hremap_levels() levels: eight where eight levels of every field of the launch fit, else four.
+const int HREMAP_MAX_FIELDS = 8, HREMAP_PASS = 4, HREMAP_PASS_TESTED = 2, HREMAP_LEVELS = 4, HREMAP_LEVELS_FEW = 8;
+const int HREMAP_STRICT = 0, HREMAP_RENORM = 1;
+constexpr int hremap_pass_fields(bool tested)
+{
+  return tested ? HREMAP_PASS_TESTED : HREMAP_PASS;
+}
+constexpr int hremap_levels(int nfields, bool tested) // nfields: of a launch
+{
+  return nfields * HREMAP_LEVELS_FEW <= (tested ? 8 : 16) ? HREMAP_LEVELS_FEW : HREMAP_LEVELS;
+}
+struct HremapParams
+{
+  int mode;    // HREMAP_*
+  int nfields; // of this launch, 1 .. hremap_pass_fields(tested)
+  int f0;
+  int ndst, nslices;
+  int nlev, lev0, call_nlev;
+  int chunk;  // levels per workgroup: grid.y = ceil(nlev / chunk) (the caller's, from hremap_shape)
+  int tested; // 0: every level of every field of the call is ALL_DEFINED, no value is tested
+  float undef;
+  double min_frac;
+  long in_stride, out_stride;
+  const float* fields[HREMAP_PASS];
+  float* out[HREMAP_PASS];
+  const u64* slice_off;   // [nslices]
+  const int* slice_width; // [nslices]
+  const int* len;         // [nslices * 64]
+  const double* wall;     // [nslices * 64]
+  const void* entries;    // 8-byte (col, w) pairs, slice_off[s] + r * 64 + lane
+  const unsigned int* lev_bits;
+  u64* n_undefined;
+};
+// The launch shape: ceil(nslices / 4) workgroups per level chunk, and the levels cut into chunks of ONE register block
+// (hremap_levels(nfields, tested), nfields the fields per launch of the call), so that the tables are read once per chunk
+// -- but shorter chunks, down to one level, where it takes that to give every CU eight workgroups, the target of
+// hinterp_plan (few destinations: DESIGN.md 4.23, the measurement).  (MIFC_HREMAP_LEVEL_CHUNK overrides the chunk; a
+// longer one walks several register blocks and reads the tables once per block.)
+struct HremapShape
+{
+  int blocks, chunk, level_chunks;
+};
+HremapShape hremap_shape(int nslices, int nlev, int nfields, bool tested);
+hipError_t launch_hremap(const HremapParams& prm, hipStream_t stream);
+
 // ------------------------------------ vector pairs of level batches rotated on the grid (mifc_vrotate.hip), EXTENSION
 // One launch rotates `nlev` levels of `npairs` pairs (u_q = fields[2q], v_q = fields[2q + 1]) at `n` cells by rule R of
 // include/mifc.h: a streaming kernel.  A lane owns V consecutive cells (vec4: four through 16-byte accesses, as in

@@ -1,6 +1,6 @@
 // mifc_levelbatch.h -- the host driver of the entries that walk level batches column by column (mifc_capi_vinterp.hip,
 // mifc_capi_vlayer.hip, mifc_capi_vderiv.hip, mifc_capi_vcumul.hip, mifc_capi_vparcel.hip; the head, the refusals and the level table also serve
-// mifc_capi_hinterp.hip, which samples the levels instead of walking them; mifc_capi_pvort.hip differences along the rows too, its bands carry neighbour rows): the head of such a call and the refusals
+// mifc_capi_hinterp.hip, which samples the levels instead of walking them, and mifc_capi_hremap.hip, which regrids them by a weight table; mifc_capi_pvort.hip differences along the rows too, its bands carry neighbour rows): the head of such a call and the refusals
 // that read only it, the overlap rule, the device table of the per-level scalars (for the `levels` form of the vertical
 // derivative its weights too), and where the planes of the call are on the device -- the caller's own for device memory, a
 // band of rows at a time for host memory (columns are independent, so a band of every level is a complete problem; where
