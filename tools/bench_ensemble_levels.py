@@ -9,22 +9,14 @@ algorithmic bytes (nmem + nproducts) x 4 B per cell, as a fraction of 8 TB/s ove
     python tools/bench_ensemble_levels.py   -> two JSON lines (fused, yardstick) per (nlev, product set)
 """
 import json
-import os
-import sys
-import time
+import statistics
 
-import numpy as np
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*: measurement build
-
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
+import mi_fieldcalc_amd as fc
 
 NX, NY, NMEM = 1440, 720, 51
-PEAK = 8000.0  # GB/s
 ROUNDS = 9
 THRESHOLDS = (271.0, 273.0, 276.0)
 SETS = {
@@ -34,27 +26,13 @@ SETS = {
 }
 
 
-def timed(ctx, call):
-    call()  # warm-up
-    torch.cuda.synchronize()
-    ts, ks = [], []
-    for _ in range(ROUNDS):
-        ctx.timing_begin()
-        t0 = time.perf_counter()
-        call()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-        ks.append(ctx.timing_end_ms())
-    return ts, ks
-
-
 def report(what, name, nlev, nprod, ts, ks):
     alg = (NMEM + nprod) * 4 * nlev * NX * NY
-    kms = float(np.median(ks))
+    kms = float(statistics.median(ks))
     print(json.dumps({"call": what, "products": name, "nproducts": nprod, "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev,
-                      "ms": round(float(np.median(ts)), 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
+                      "ms": round(float(statistics.median(ts)), 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
                       "kernel_ms": round(kms, 4), "kernel_ms_min": round(min(ks), 4), "kernel_ms_max": round(max(ks), 4),
-                      "algorithmic_bytes": alg, "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}), flush=True)
+                      "algorithmic_bytes": alg, "kernel_frac_of_8TBps": bk.rate(alg, kms)[1]}), flush=True)
     return kms
 
 
@@ -79,27 +57,20 @@ def main():
             flags = [fc.SOME_DEFINED] * NMEM
             for name, products in SETS.items():
                 out = torch.empty((len(products), nlev, NY, NX), device=dev, dtype=torch.float32)
-                ts, ks = timed(ctx, lambda: ctx.ensembleStatistics(members, products, out=out))  # noqa: B023
-                fused = report("ensembleStatistics", name, nlev, len(products), ts, ks)
+                ts, ks = bk.alternate(ctx, {"fused": (lambda: ctx.ensembleStatistics(members, products, out=out), bk.WALL_KERNEL)}, ROUNDS)  # noqa: B023
+                fused = report("ensembleStatistics", name, nlev, len(products), ts["fused"], ks["fused"])
 
-                def yardstick():
+                def level(l, lv):
+                    for k, spec in enumerate(products):  # noqa: B023
+                        assert single_field(ctx, spec, lv, flags, out[k, l]) is not None  # noqa: B023
+
+                def yardstick(section):
                     # at most 16 launches are timed per section: one section per level, summed
-                    k_ms = 0.0
                     for l, lv in enumerate(per_level):  # noqa: B023
-                        ctx.timing_begin()
-                        for k, spec in enumerate(products):  # noqa: B023
-                            assert single_field(ctx, spec, lv, flags, out[k, l]) is not None  # noqa: B023
-                        torch.cuda.synchronize()
-                        k_ms += ctx.timing_end_ms()
-                    return k_ms
+                        section(lambda l=l, lv=lv: level(l, lv))
 
-                yardstick()  # warm-up
-                ts, ks = [], []
-                for _ in range(ROUNDS):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    ks.append(yardstick())
-                    ts.append((time.perf_counter() - t0) * 1e3)
+                ts, ks = bk.alternate(ctx, {"yardstick": (yardstick, bk.WALL_SECTIONS)}, ROUNDS)
+                ts, ks = ts["yardstick"], ks["yardstick"]
                 base = report("single-field entries (yardstick, one call per level and product)", name, nlev, len(products), ts, ks)
                 print(json.dumps({"products": name, "nlev": nlev, "kernel_ms_fused": round(fused, 4), "kernel_ms_yardstick": round(base, 4),
                                   "yardstick_kernel_spread_ms": round(max(ks) - min(ks), 4), "fused_over_yardstick": round(fused / base, 4)}), flush=True)

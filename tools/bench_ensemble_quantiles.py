@@ -8,38 +8,25 @@ cell: every member read once, every output written once), fraction of 8 TB/s -- 
     python tools/bench_ensemble_quantiles.py   -> one JSON line per (nlev, nq, method), then one per yardstick
 """
 import json
-import os
-import sys
-import time
 
-import numpy as np
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*: measurement build
-
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
+import mi_fieldcalc_amd as fc
 
 NX, NY, NMEM = 1440, 720, 51
-PEAK = 8000.0  # GB/s
 ROUNDS = 9
 PS = {1: [50.0], 5: [10.0, 25.0, 50.0, 75.0, 90.0]}
 
 
 def timed(ctx, call):
-    assert call() is not None, ctx.last_error()  # warm-up
-    torch.cuda.synchronize()
-    ts, ks = [], []
-    for _ in range(ROUNDS):
-        ctx.timing_begin()
-        t0 = time.perf_counter()
-        call()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-        ks.append(ctx.timing_end_ms())
-    return float(np.median(ts)), float(np.median(ks))
+    assert call() is not None, ctx.last_error()
+    ts, ks = bk.alternate(ctx, {"call": (call, bk.WALL_KERNEL)}, ROUNDS)
+    return bk.stats(ts["call"], "ms")["ms"], bk.stats(ks["call"])["kernel_ms"]
+
+
+def fractions(alg, ms, kms):
+    return {"algorithmic_bytes": alg, "frac_of_8TBps": bk.rate(alg, ms)[1], "kernel_frac_of_8TBps": bk.rate(alg, kms)[1]}
 
 
 def main():
@@ -53,11 +40,8 @@ def main():
                 out = torch.empty((nq, nlev, NY, NX), device=dev, dtype=torch.float32)
                 for method in ("lower", "linear"):
                     ms, kms = timed(ctx, lambda: ctx.ensembleQuantiles(members, PS[nq], method=method, out=out))  # noqa: B023
-                    alg = (NMEM + nq) * 4 * cells
                     print(json.dumps({"call": "ensembleQuantiles", "method": method, "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev, "nq": nq,
-                                      "ms": round(ms, 4), "kernel_ms": round(kms, 4), "algorithmic_bytes": alg,
-                                      "frac_of_8TBps": round(alg / ms / 1e6 / PEAK, 4),
-                                      "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}), flush=True)
+                                      "ms": ms, "kernel_ms": kms, **fractions((NMEM + nq) * 4 * cells, ms, kms)}), flush=True)
             # yardstick: meanValue over the same members, one call per level (it takes 2-D fields)
             mean_out = torch.empty((NY, NX), device=dev, dtype=torch.float32)
             per_level = [[members[j, l] for j in range(NMEM)] for l in range(nlev)]
@@ -69,10 +53,8 @@ def main():
                 return r
 
             ms, kms = timed(ctx, means)
-            alg = (NMEM + 1) * 4 * cells
-            print(json.dumps({"call": "meanValue (yardstick, one call per level)", "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev, "ms": round(ms, 4),
-                              "kernel_ms": round(kms, 4), "algorithmic_bytes": alg, "frac_of_8TBps": round(alg / ms / 1e6 / PEAK, 4),
-                              "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}), flush=True)
+            print(json.dumps({"call": "meanValue (yardstick, one call per level)", "nmem": NMEM, "nx": NX, "ny": NY, "nlev": nlev, "ms": ms,
+                              "kernel_ms": kms, **fractions((NMEM + 1) * 4 * cells, ms, kms)}), flush=True)
             del members
 
 

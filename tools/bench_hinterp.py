@@ -16,21 +16,15 @@ is float32 arithmetic with zero padding and no undefined values: a comparison of
 """
 import json
 import math
-import os
 import sys
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
+import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
 
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 ROUNDS = 9
 VALUES_PER_POINT = {"nearest": 1, "bilinear": 4, "bicubic": 16}
 
@@ -38,33 +32,6 @@ VALUES_PER_POINT = {"nearest": 1, "bilinear": 4, "bicubic": 16}
 def algorithmic_bytes(nx, ny, nlev, nf, npos, method):
     needed = VALUES_PER_POINT[method] * npos
     return 4 * (2 * npos + nf * nlev * npos + nf * nlev * min(nx * ny, needed))
-
-
-def time_alternating(ctx, calls):
-    """calls: name -> (callable, is_mifc).  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call, _ in calls.values():
-        call()  # warm-up: code object, scratch, the allocator's blocks
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, (call, is_mifc) in calls.items():
-            if is_mifc:
-                ctx.timing_begin()
-                call()
-                torch.cuda.synchronize()
-                ms[name].append(ctx.timing_end_ms())
-            else:
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                call()
-                t1.record()
-                torch.cuda.synchronize()
-                ms[name].append(t0.elapsed_time(t1))
-    return ms
-
-
-def stats(ts):
-    return {"kernel_ms": round(float(np.median(ts)), 4), "kernel_ms_min": round(min(ts), 4), "kernel_ms_spread": round(max(ts) - min(ts), 4)}
 
 
 def rotated_grid(nx, ny, gx, gy, dev):
@@ -88,17 +55,17 @@ def run_case(ctx, case, fields, x, y, lines):
     grid = torch.stack([2 * x / max(nx - 1, 1) - 1, 2 * y / max(ny - 1, 1) - 1], dim=-1).view(1, -1, x.shape[-1], 2).contiguous()
     calls = {}
     for method in ("nearest", "bilinear", "bicubic"):
-        calls["mifc %s" % method] = (lambda method=method: ctx.hinterp_levels(fields, x, y, method, out=out), True)
-    calls["mifc bilinear, ALL_DEFINED"] = (lambda: ctx.hinterp_levels(fields, x, y, "bilinear", fdefined_in=every, out=out), True)
+        calls["mifc %s" % method] = lambda method=method: ctx.hinterp_levels(fields, x, y, method, out=out)
+    calls["mifc bilinear, ALL_DEFINED"] = lambda: ctx.hinterp_levels(fields, x, y, "bilinear", fdefined_in=every, out=out)
     for mode in ("nearest", "bilinear"):
-        calls["grid_sample %s" % mode] = (lambda mode=mode: F.grid_sample(image, grid, mode=mode, padding_mode="zeros", align_corners=True), False)
-    ms = time_alternating(ctx, calls)
+        calls["grid_sample %s" % mode] = (lambda mode=mode: F.grid_sample(image, grid, mode=mode, padding_mode="zeros", align_corners=True), bk.EVENTS)
+    _, ms = bk.alternate(ctx, calls, ROUNDS)
     results = {}
     for name, ts in ms.items():
         method = name.split()[1].rstrip(",")
-        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, "npos": npos, **stats(ts),
+        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, "npos": npos, **bk.stats(ts),
              "algorithmic_bytes": algorithmic_bytes(nx, ny, nlev, nf, npos, method)}
-        r["GBps"] = round(r["algorithmic_bytes"] / r["kernel_ms"] / 1e6, 1)
+        r["GBps"] = bk.rate(r["algorithmic_bytes"], r["kernel_ms"])[0]
         results[name] = r
         print(json.dumps(r), flush=True)
     for name, r in results.items():
@@ -109,9 +76,8 @@ def run_case(ctx, case, fields, x, y, lines):
 
 
 def main():
-    small = "--small" in sys.argv
-    nx, ny, nlev = (360, 180, 24) if small else (NX, NY, NLEV)
-    gx, gy, npts, nf = (500, 250, 500, 4) if small else (2000, 1000, 2000, 8)
+    nx, ny, nlev = bk.shape(sys.argv)
+    gx, gy, npts, nf = bk.shape(sys.argv, (2000, 1000, 2000, 8), (500, 250, 500, 4))
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2025)
     lines = []

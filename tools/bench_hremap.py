@@ -18,23 +18,17 @@ slice) once per level chunk and launch -- with the rate they give over the kerne
     python tools/bench_hremap.py --only=ac      -> the cases whose letter is named (MIFC_HREMAP_LEVEL_CHUNK=n for an A/B of the level chunks)
 """
 import json
-import os
 import sys
-import time
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
+from mi_fieldcalc_amd import hremap
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-from mi_fieldcalc_amd import hremap  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 ROUNDS = 9
+MIFC, FOREIGN = bk.WALL_KERNEL, bk.WALL  # how a library call and a torch call are timed
 
 
 def table_bytes(rowptr):
@@ -45,29 +39,6 @@ def table_bytes(rowptr):
     padded[:n.size] = n
     widths = padded.reshape(nslices, 64).max(axis=1)
     return int(8 * 64 * widths.sum() + 12 * 64 * nslices + 12 * nslices)
-
-
-def time_alternating(ctx, calls):
-    """calls: name -> (callable, is_mifc).  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call, _ in calls.values():
-        call()  # warm-up: code object, scratch, the allocator's blocks
-    torch.cuda.synchronize()
-    call_ms, kernel_ms = {name: [] for name in calls}, {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, (call, is_mifc) in calls.items():
-            if is_mifc:
-                ctx.timing_begin()
-            t0 = time.perf_counter()
-            call()
-            torch.cuda.synchronize()
-            call_ms[name].append(1e3 * (time.perf_counter() - t0))
-            if is_mifc:
-                kernel_ms[name].append(ctx.timing_end_ms())
-    return call_ms, kernel_ms
-
-
-def stats(ts, key):
-    return {key: round(float(np.median(ts)), 4), key + "_min": round(min(ts), 4), key + "_spread": round(max(ts) - min(ts), 4)}
 
 
 def random_rows(ndst, nsrc, lo, hi, seed):
@@ -89,9 +60,9 @@ def run_case(ctx, case, fields, table, dst_shape, lines, profile):
     every = np.zeros((nf, nlev), np.int32)  # ALL_DEFINED
     out = torch.empty((nf, nlev, ndst), device=dev, dtype=torch.float32)
     with hremap.Plan(ctx, rowptr, col, w, nsrc=ny * nx) as plan:
-        calls = {"hremap strict, ALL_DEFINED": (lambda: hremap.hremap_levels(ctx, plan, fields, "strict", fdefined_in=every, out=out), True),
-                 "hremap strict, tested": (lambda: hremap.hremap_levels(ctx, plan, fields, "strict", out=out), True),
-                 "hremap renorm, tested": (lambda: hremap.hremap_levels(ctx, plan, fields, "renorm", 0.5, out=out), True)}
+        calls = {"hremap strict, ALL_DEFINED": (lambda: hremap.hremap_levels(ctx, plan, fields, "strict", fdefined_in=every, out=out), MIFC),
+                 "hremap strict, tested": (lambda: hremap.hremap_levels(ctx, plan, fields, "strict", out=out), MIFC),
+                 "hremap renorm, tested": (lambda: hremap.hremap_levels(ctx, plan, fields, "renorm", 0.5, out=out), MIFC)}
         if profile:
             for call, _ in calls.values():
                 for _ in range(3):
@@ -106,17 +77,17 @@ def run_case(ctx, case, fields, table, dst_shape, lines, profile):
             yy, xx = torch.meshgrid(ys, xs, indexing="ij")
             xx, yy = xx.contiguous(), yy.contiguous()
             hout = torch.empty((nf, nlev, gy, gx), device=dev, dtype=torch.float32)
-            calls["hinterp bilinear, ALL_DEFINED"] = (lambda: ctx.hinterp_levels(fields, xx, yy, "bilinear", fdefined_in=every, out=hout), True)
+            calls["hinterp bilinear, ALL_DEFINED"] = (lambda: ctx.hinterp_levels(fields, xx, yy, "bilinear", fdefined_in=every, out=hout), MIFC)
         try:  # the same table as a CSR tensor, the batch laid out (nsrc, nf * nlev) beforehand
             csr = torch.sparse_csr_tensor(torch.from_numpy(rowptr.astype(np.int64)).to(dev), torch.from_numpy(col.astype(np.int64)).to(dev),
                                           torch.from_numpy(w).to(dev), size=(ndst, ny * nx))
             dense = fields.reshape(nf * nlev, ny * nx).t().contiguous()
             torch.sparse.mm(csr, dense)
             torch.cuda.synchronize()
-            calls["torch.sparse.mm"] = (lambda: torch.sparse.mm(csr, dense), False)
+            calls["torch.sparse.mm"] = (lambda: torch.sparse.mm(csr, dense), FOREIGN)
         except Exception as e:  # noqa: BLE001
             notes["torch.sparse.mm"] = "not run on the device by this torch build: %s" % (str(e).splitlines()[0][:160],)
-        call_ms, kernel_ms = time_alternating(ctx, calls)
+        call_ms, kernel_ms = bk.alternate(ctx, calls, ROUNDS)
         hremap.hremap_levels(ctx, plan, fields, "strict", fdefined_in=every, out=out)
         launch = hremap.last_hremap_form(ctx)
         hremap.hremap_levels(ctx, plan, fields, "strict", out=out)
@@ -127,14 +98,14 @@ def run_case(ctx, case, fields, table, dst_shape, lines, profile):
     touched = int(np.unique(col).size)
     results = {}
     for name in calls:
-        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, "ndst": ndst, "nnz": int(rowptr[-1]), **stats(call_ms[name], "call_ms")}
+        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, "ndst": ndst, "nnz": int(rowptr[-1]), **bk.stats(call_ms[name], "call_ms")}
         if kernel_ms[name]:
-            r.update(stats(kernel_ms[name], "kernel_ms"))
+            r.update(bk.stats(kernel_ms[name], "kernel_ms"))
         if name.startswith("hremap"):
             form = launch if "ALL_DEFINED" in name else (launch_renorm if "renorm" in name else launch_tested)
             r["algorithmic_bytes"] = 4 * nf * nlev * (touched + ndst) + tables * form["level_chunks"] * form["launches"]
             r["table_bytes_once"] = tables
-            r["GBps_over_kernel_time"] = round(r["algorithmic_bytes"] / r["kernel_ms"] / 1e6, 1)
+            r["GBps_over_kernel_time"] = bk.rate(r["algorithmic_bytes"], r["kernel_ms"])[0]
             r["launch"] = form
         results[name] = r
         print(json.dumps(r), flush=True)
@@ -153,7 +124,7 @@ def run_case(ctx, case, fields, table, dst_shape, lines, profile):
 def main():
     small, profile = "--small" in sys.argv, "--profile" in sys.argv
     only = "".join(a.split("=", 1)[1] for a in sys.argv if a.startswith("--only=")) or "abc"
-    nx, ny, nlev = (360, 180, 24) if small else (NX, NY, NLEV)
+    nx, ny, nlev = bk.shape(sys.argv)
     nf_c = 4 if small else 8
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2025)

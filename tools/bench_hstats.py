@@ -15,51 +15,19 @@ speed, never of results.
     python tools/bench_hstats.py [--small]   -> one JSON line per call, then one comparison line per mifc call
 """
 import json
-import os
 import sys
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
-
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
+import mi_fieldcalc_amd as fc
 
 ROUNDS = 7
 
 
 def algorithmic_bytes(nx, ny, nlev, nf, weighted, minus=False):
     return 4 * nx * ny * (nlev * nf * (2 if minus else 1) + (1 if weighted else 0))
-
-
-def time_alternating(ctx, calls):
-    """calls: name -> (callable, is_mifc).  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call, _ in calls.values():
-        call()  # warm-up: code object, scratch, the allocator's blocks
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, (call, is_mifc) in calls.items():
-            if is_mifc:
-                ctx.timing_begin()
-                call()
-                torch.cuda.synchronize()
-                ms[name].append(ctx.timing_end_ms())
-            else:
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                call()
-                t1.record()
-                torch.cuda.synchronize()
-                ms[name].append(t0.elapsed_time(t1))
-    return ms
-
-
-def stats(ts):
-    return {"kernel_ms": round(float(np.median(ts)), 4), "kernel_ms_min": round(min(ts), 4), "kernel_ms_spread": round(max(ts) - min(ts), 4)}
 
 
 def yardstick(x, mode, extremes):
@@ -80,20 +48,20 @@ def run_case(ctx, case, fields, weight, lines, modes=("area", "rows")):
             what = "+".join(products)
             for w in ((None, weight) if weight is not None else (None,)):
                 name = "mifc %s %s%s" % (mode, what, ", weight" if w is not None else "")
-                calls[name] = (lambda mode=mode, products=products, w=w, out=out: ctx.hstats_levels(fields, weight=w, mode=mode, products=products, out=out), True)
+                calls[name] = lambda mode=mode, products=products, w=w, out=out: ctx.hstats_levels(fields, weight=w, mode=mode, products=products, out=out)
                 meta[name] = (mode, len(products) == 2, w is not None)
             name = "torch %s %s" % (mode, what)
-            calls[name] = (lambda mode=mode, ext=len(products) == 2: yardstick(fields, mode, ext), False)
+            calls[name] = (lambda mode=mode, ext=len(products) == 2: yardstick(fields, mode, ext), bk.EVENTS)
             meta[name] = (mode, len(products) == 2, False)
         name = "mifc %s moments+extremes, ALL_DEFINED" % mode
-        calls[name] = (lambda mode=mode, out=out: ctx.hstats_levels(fields, mode=mode, fdefined_in=every, out=out), True)
+        calls[name] = lambda mode=mode, out=out: ctx.hstats_levels(fields, mode=mode, fdefined_in=every, out=out)
         meta[name] = (mode, True, False)
-    ms = time_alternating(ctx, calls)
+    _, ms = bk.alternate(ctx, calls, ROUNDS)
     results = {}
     for name, ts in ms.items():
         mode, ext, weighted = meta[name]
-        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **stats(ts), "algorithmic_bytes": algorithmic_bytes(nx, ny, nlev, nf, weighted)}
-        r["GBps"] = round(r["algorithmic_bytes"] / r["kernel_ms"] / 1e6, 1)
+        r = {"case": case, "call": name, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **bk.stats(ts), "algorithmic_bytes": algorithmic_bytes(nx, ny, nlev, nf, weighted)}
+        r["GBps"] = bk.rate(r["algorithmic_bytes"], r["kernel_ms"])[0]
         results[name] = r
         print(json.dumps(r), flush=True)
     for name, r in results.items():
@@ -105,9 +73,8 @@ def run_case(ctx, case, fields, weight, lines, modes=("area", "rows")):
 
 
 def main():
-    small = "--small" in sys.argv
-    nx, ny, nlev = (360, 180, 24) if small else (1440, 720, 137)
-    side, npts = (1000, 200000) if small else (4000, 2000000)
+    nx, ny, nlev = bk.shape(sys.argv)
+    side, npts = bk.shape(sys.argv, (4000, 2000000), (1000, 200000))
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2025)
     lines = []

@@ -8,28 +8,23 @@ tests/neighbour_ref_shim.cc), scaled to the batch.
     python tools/bench_neighbour.py [NLEV] [--no-cpu]   -> one JSON line per (function, compute, r, step)
 """
 import json
-import os
 import sys
 import tempfile
 import time
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*: measurement build
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mi_fieldcalc_amd as fc
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
+bk.tests_on_path()
 import neighbour_cases as nc  # noqa: E402  (CPU baseline and the seeded field only)
 
 NX, NY = 1440, 720
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 NLEV = int(ARGS[0]) if ARGS else 51
 NO_CPU = "--no-cpu" in sys.argv
-PEAK = 8000.0  # GB/s
 ROUNDS = 7
 
 # (which, compute, constants, r, step)
@@ -55,20 +50,12 @@ def main():
         for which, compute, consts, r, step in CASES:
             call = lambda: ctx.neighbour_levels(which, compute, field, consts, out=out)  # noqa: E731
             assert call() is not None, ctx.last_error()
-            torch.cuda.synchronize()
-            ts, ks = [], []
-            for _ in range(ROUNDS):
-                ctx.timing_begin()
-                t0 = time.perf_counter()
-                call()
-                torch.cuda.synchronize()
-                ts.append((time.perf_counter() - t0) * 1e3)
-                ks.append(ctx.timing_end_ms())
-            ms, kms = float(np.median(ts)), float(np.median(ks))
+            ts, ks = bk.alternate(ctx, {"call": (call, bk.WALL_KERNEL)}, ROUNDS)
+            ms, kms = bk.stats(ts["call"], "ms")["ms"], bk.stats(ks["call"])["kernel_ms"]
             alg = 8 * cells
             rec = {"function": "neighbourProbFunctions" if which == "prob" else "neighbourFunctions", "compute": compute, "r": r, "step": step,
-                   "nx": NX, "ny": NY, "nlev": NLEV, "ms": round(ms, 4), "kernel_ms": round(kms, 4), "algorithmic_bytes": alg,
-                   "frac_of_8TBps": round(alg / ms / 1e6 / PEAK, 4), "kernel_frac_of_8TBps": round(alg / kms / 1e6 / PEAK, 4) if kms > 0 else None}
+                   "nx": NX, "ny": NY, "nlev": NLEV, "ms": ms, "kernel_ms": kms, "algorithmic_bytes": alg,
+                   "frac_of_8TBps": bk.rate(alg, ms)[1], "kernel_frac_of_8TBps": bk.rate(alg, kms)[1]}
             if shim is not None:
                 res = np.empty((NY, NX), np.float32)
                 t0 = time.perf_counter()

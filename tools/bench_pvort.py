@@ -14,23 +14,15 @@ the two spreads.
     python tools/bench_pvort.py [--small]   -> one JSON line per case, then one comparison line per form and method
 """
 import json
-import os
 import sys
 
-import numpy as np
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
+from mi_fieldcalc_amd import pvort
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-from mi_fieldcalc_amd import pvort  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 ROUNDS = 9
-PEAK_GBPS = 8000.0
 KINDS = ("hybrid", "field", "levels")
 METHODS = ("centred", "weighted")
 TILE_ROWS = 8
@@ -59,48 +51,14 @@ def chain_bytes(nx, ny, nlev, kind):
     return (3 + 2 * 2 + 17) * nlev * 4 * nx * ny + vderiv_bytes(nx, ny, nlev, kind)
 
 
-def timed(ctx, call):
-    """The kernel time of one call (or of a few: a timing section holds 16 launches)."""
-    ctx.timing_begin()
-    call()
-    torch.cuda.synchronize()
-    ms = ctx.timing_end_ms()
-    if ms < 0:
-        raise RuntimeError("a timing section with too many launches")
-    return ms
-
-
-def kernel_ms_alternating(ctx, calls):
-    """calls: name -> callable(section), which runs its calls through section(callable) -- one timing section each -- and
-    returns nothing.  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call in calls.values():
-        call(lambda part: part())  # warm-up: code object, scratch
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, call in calls.items():
-            parts = []
-            call(lambda part: parts.append(timed(ctx, part)))  # noqa: B023
-            ms[name].append(sum(parts))
-    return ms
-
-
-def stats(ts):
-    return {"kernel_ms": round(float(np.median(ts)), 4), "kernel_ms_min": round(min(ts), 4), "kernel_ms_spread": round(max(ts) - min(ts), 4)}
-
-
 def main():
-    nx, ny, nlev = (360, 180, 24) if "--small" in sys.argv else (NX, NY, NLEV)
+    nx, ny, nlev = bk.shape(sys.argv)
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2024)
-    eta = np.linspace(0.01, 1, nlev) ** 3
-    alevel, blevel = (1000 * (eta - eta ** 2)).astype(np.float32), (eta ** 2).astype(np.float32)
-    levels = (alevel + blevel * np.float32(1000)).astype(np.float32)
-    yy, xx = torch.meshgrid(torch.linspace(0, 6.28, ny, device=dev), torch.linspace(0, 12.56, nx, device=dev), indexing="ij")
-    ps = (780 + 260 * torch.sin(xx) * torch.cos(yy) + torch.randn((ny, nx), generator=gen, device=dev)).clamp(520, 1040).contiguous()
+    alevel, blevel, levels, ps, make_coord = bk.hybrid_atmosphere(nx, ny, nlev, dev, gen)
     uvt = torch.randn((3, nlev, ny, nx), generator=gen, device=dev, dtype=torch.float32) * 3 + 250
     u, v, th = uvt[0], uvt[1], uvt[2]
-    coord = (torch.from_numpy(alevel).to(dev)[:, None, None] + torch.from_numpy(blevel).to(dev)[:, None, None] * ps[None]).contiguous()
+    coord = make_coord()
     xm = torch.full((ny, nx), 2e-5, device=dev) + 1e-6 * torch.rand((ny, nx), generator=gen, device=dev)
     ym = torch.full((ny, nx), 2e-5, device=dev) + 1e-6 * torch.rand((ny, nx), generator=gen, device=dev)
     f = torch.full((ny, nx), 1e-4, device=dev) + 1e-5 * torch.rand((ny, nx), generator=gen, device=dev)
@@ -144,25 +102,25 @@ def main():
 
         for kind in KINDS:
             for method in METHODS:
-                calls = {"pvort": lambda section: section(lambda: fused(kind, method)), "chain": lambda section: chain(kind, method, section),  # noqa: B023
-                         "vderiv x3": lambda section: section(lambda: vderiv(kind, method))}  # noqa: B023
-                ms = kernel_ms_alternating(ctx, calls)
+                # a timing section holds 16 launches: the chain runs its calls through section(), one timing section each
+                calls = {"pvort": lambda: fused(kind, method), "chain": (lambda section: chain(kind, method, section), bk.SECTIONS),  # noqa: B023
+                         "vderiv x3": lambda: vderiv(kind, method)}  # noqa: B023
+                _, ms = bk.alternate(ctx, calls, ROUNDS)
                 form = pvort.last_pvort_form(ctx)
                 # the chain rounds every intermediate to float: the same field, not the same bits
                 inner = (slice(None), slice(1, -1), slice(1, -1))
                 close = (out[inner] - chain_out[inner]).abs() <= 1e-3 * out[inner].abs() + 1e-3 * out[inner].abs().mean()
-                st = {name: stats(ts) for name, ts in ms.items()}
+                st = {name: bk.stats(ts) for name, ts in ms.items()}
                 alg = {"pvort": pvort_bytes(nx, ny, nlev, kind), "chain": chain_bytes(nx, ny, nlev, kind), "vderiv x3": vderiv_bytes(nx, ny, nlev, kind)}
                 for name in calls:
                     r = {"call": name, "coordinate": kind, "method": method, "nx": nx, "ny": ny, "nlev": nlev, **st[name], "algorithmic_bytes": alg[name]}
-                    r["GBps"] = round(alg[name] / r["kernel_ms"] / 1e6, 1)
-                    r["share_of_8TBps"] = round(r["GBps"] / PEAK_GBPS, 3)
+                    r["GBps"], r["share_of_8TBps"] = bk.rate(alg[name], r["kernel_ms"])
                     print(json.dumps(r), flush=True)
                 p, c, b = st["pvort"], st["chain"], st["vderiv x3"]
-                model_ms = pvort_bytes(nx, ny, nlev, kind, halo=False) / PEAK_GBPS / 1e6
+                model_ms = pvort_bytes(nx, ny, nlev, kind, halo=False) / bk.PEAK_GBPS / 1e6
                 lines.append({"coordinate": kind, "method": method, "form": form, "pvort_ms": p["kernel_ms"], "chain_ms": c["kernel_ms"],
                               "speedup_over_chain": round(c["kernel_ms"] / p["kernel_ms"], 2),
-                              "not_slower_than_chain_beyond_the_two_spreads": bool(p["kernel_ms_min"] <= c["kernel_ms_min"] + c["kernel_ms_spread"] + p["kernel_ms_spread"]),
+                              "not_slower_than_chain_beyond_the_two_spreads": bk.not_slower(p, c),
                               "byte_model_ms_at_8TBps": round(model_ms, 4), "share_of_byte_model_time": round(model_ms / p["kernel_ms"], 3),
                               "GBps": round(alg["pvort"] / p["kernel_ms"] / 1e6, 1), "vderiv_x3_GBps": round(alg["vderiv x3"] / b["kernel_ms"] / 1e6, 1),
                               "share_of_vderiv_rate": round((alg["pvort"] / p["kernel_ms"]) / (alg["vderiv x3"] / b["kernel_ms"]), 3),

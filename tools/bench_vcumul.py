@@ -12,25 +12,17 @@ whole call -- staging band by band, kernels, download -- over HOST_ROUNDS calls,
     python tools/bench_vcumul.py [--small] [--host | --all]   -> one JSON line per case, then one comparison line per case
 """
 import json
-import os
 import sys
-import time
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
+from mi_fieldcalc_amd import vcumul
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-from mi_fieldcalc_amd import vcumul  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 NFS = (1, 4, 8)
 ROUNDS, HOST_ROUNDS = 9, 3
-PEAK_GBPS = 8000.0
 KINDS = ("hybrid", "field", "levels")
 # (name, method, from_, with start and base)
 CASES = (("linear, first", "linear", "first", False), ("linear, last", "linear", "last", False), ("linear, last, start+base", "linear", "last", True),
@@ -44,37 +36,6 @@ def coord_planes(kind, nlev):
 def batch_bytes(nx, ny, nlev, nf, kind, extra_planes=0):
     """Every field level and the coordinate (or ps) read once, every output level written once; the start and base planes."""
     return (nf * nlev + coord_planes(kind, nlev) + nf * nlev + extra_planes) * 4 * nx * ny
-
-
-def kernel_ms_alternating(ctx, calls):
-    """calls: name -> callable.  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call in calls.values():
-        call()  # warm-up: code object, scratch
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, call in calls.items():
-            ctx.timing_begin()
-            call()
-            torch.cuda.synchronize()
-            ms[name].append(ctx.timing_end_ms())
-    return ms
-
-
-def wall_ms_alternating(calls):
-    for call in calls.values():
-        call()
-    ms = {name: [] for name in calls}
-    for _ in range(HOST_ROUNDS):
-        for name, call in calls.items():
-            t0 = time.perf_counter()
-            call()
-            ms[name].append((time.perf_counter() - t0) * 1e3)
-    return ms
-
-
-def stats(ts, key):
-    return {key: round(float(np.median(ts)), 4), key + "_min": round(min(ts), 4), key + "_spread": round(max(ts) - min(ts), 4)}
 
 
 def make_calls(ctx, kind, fields, ps, coord, alevel, blevel, levels, start, bases, out):
@@ -100,15 +61,14 @@ def make_calls(ctx, kind, fields, ps, coord, alevel, blevel, levels, start, base
 
 
 def report(ms, key, nx, ny, nlev, nf, kind, memory, lines):
-    base = stats(ms["vderiv centred"], key)
+    base = bk.stats(ms["vderiv centred"], key)
     base_bytes = batch_bytes(nx, ny, nlev, nf, kind)
     base_gbps = base_bytes / base[key] / 1e6
     for name, ts in ms.items():
         extra = 1 + nf if name.endswith("start+base") else 0
         alg = batch_bytes(nx, ny, nlev, nf, kind, extra)
-        r = {"call": name, "memory": memory, "coordinate": kind, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **stats(ts, key), "algorithmic_bytes": alg}
-        r["GBps"] = round(alg / r[key] / 1e6, 1)
-        r["share_of_8TBps"] = round(r["GBps"] / PEAK_GBPS, 3)
+        r = {"call": name, "memory": memory, "coordinate": kind, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **bk.stats(ts, key), "algorithmic_bytes": alg}
+        r["GBps"], r["share_of_8TBps"] = bk.rate(alg, r[key])
         print(json.dumps(r), flush=True)
         if name != "vderiv centred":
             lines.append({"call": name, "memory": memory, "coordinate": kind, "nfields": nf, "GBps": r["GBps"], "vderiv_centred_GBps": round(base_gbps, 1),
@@ -116,16 +76,12 @@ def report(ms, key, nx, ny, nlev, nf, kind, memory, lines):
 
 
 def main():
-    nx, ny, nlev = (360, 180, 24) if "--small" in sys.argv else (NX, NY, NLEV)
+    nx, ny, nlev = bk.shape(sys.argv)
     on_device = "--host" not in sys.argv
     on_host = "--host" in sys.argv or "--all" in sys.argv
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2024)
-    eta = np.linspace(0.01, 1, nlev) ** 3
-    alevel, blevel = (1000 * (eta - eta ** 2)).astype(np.float32), (eta ** 2).astype(np.float32)
-    levels = (alevel + blevel * np.float32(1000)).astype(np.float32)
-    yy, xx = torch.meshgrid(torch.linspace(0, 6.28, ny, device=dev), torch.linspace(0, 12.56, nx, device=dev), indexing="ij")
-    ps = (780 + 260 * torch.sin(xx) * torch.cos(yy) + torch.randn((ny, nx), generator=gen, device=dev)).clamp(520, 1040).contiguous()
+    alevel, blevel, levels, ps, make_coord = bk.hybrid_atmosphere(nx, ny, nlev, dev, gen)
     start = {"first": torch.full((ny, nx), 0.005, device=dev), "last": (ps + 5).contiguous()}
     bases = torch.rand((max(NFS), ny, nx), generator=gen, device=dev) * 2000
     lines = []
@@ -133,12 +89,12 @@ def main():
         if on_device:
             ctx.use_torch_stream()
             all_fields = torch.randn((max(NFS), nlev, ny, nx), generator=gen, device=dev, dtype=torch.float32) * 3 + 250
-            coord = (torch.from_numpy(alevel).to(dev)[:, None, None] + torch.from_numpy(blevel).to(dev)[:, None, None] * ps[None]).contiguous()
+            coord = make_coord()
             out_all = torch.empty((max(NFS), nlev, ny, nx), device=dev, dtype=torch.float32)
             for nf in NFS:
                 for kind in KINDS:
                     calls = make_calls(ctx, kind, all_fields[:nf], ps, coord, alevel, blevel, levels, start, bases, out_all[:nf])
-                    report(kernel_ms_alternating(ctx, calls), "kernel_ms", nx, ny, nlev, nf, kind, "device", lines)
+                    report(bk.alternate(ctx, calls, ROUNDS)[1], "kernel_ms", nx, ny, nlev, nf, kind, "device", lines)
             del all_fields, coord, out_all
             torch.cuda.empty_cache()
         if on_host:
@@ -152,7 +108,8 @@ def main():
             for nf in NFS:
                 for kind in ("hybrid",):
                     calls = make_calls(ctx, kind, h_fields[:nf], h_ps, h_coord, alevel, blevel, levels, h_start, h_bases, h_out[:nf])
-                    report(wall_ms_alternating(calls), "wall_ms", nx, ny, nlev, nf, kind, "host", lines)
+                    walled = {name: (call, bk.WALL) for name, call in calls.items()}
+                    report(bk.alternate(ctx, walled, HOST_ROUNDS)[0], "wall_ms", nx, ny, nlev, nf, kind, "host", lines)
     for line in lines:
         print(json.dumps(line), flush=True)
 

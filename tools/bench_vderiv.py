@@ -12,23 +12,15 @@ rates, not of the times.
     python tools/bench_vderiv.py [--small]   -> one JSON line per case, then one comparison line per case
 """
 import json
-import os
 import sys
 
-import numpy as np
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 NFS = (1, 2, 4, 8)
 ROUNDS = 9
-PEAK_GBPS = 8000.0
 KINDS = ("hybrid", "field", "levels")
 METHODS = ("centred", "weighted")
 WHAT = {"derivatives": None, "magnitude only": "only", "both": "also"}
@@ -47,36 +39,13 @@ def vinterp_bytes(nx, ny, nlev, nf, nt, hybrid):
     return (nf * nlev + (0 if hybrid else nlev) + 1 + nf * nt) * 4 * nx * ny
 
 
-def kernel_ms_alternating(ctx, calls):
-    """calls: name -> callable.  One warm-up each, then ROUNDS rounds in which every call is timed once, in turn."""
-    for call in calls.values():
-        call()  # warm-up: code object, scratch
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, call in calls.items():
-            ctx.timing_begin()
-            call()
-            torch.cuda.synchronize()
-            ms[name].append(ctx.timing_end_ms())
-    return ms
-
-
-def stats(ts):
-    return {"kernel_ms": round(float(np.median(ts)), 4), "kernel_ms_min": round(min(ts), 4), "kernel_ms_spread": round(max(ts) - min(ts), 4)}
-
-
 def main():
-    nx, ny, nlev = (360, 180, 24) if "--small" in sys.argv else (NX, NY, NLEV)
+    nx, ny, nlev = bk.shape(sys.argv)
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2024)
-    eta = np.linspace(0.01, 1, nlev) ** 3
-    alevel, blevel = (1000 * (eta - eta ** 2)).astype(np.float32), (eta ** 2).astype(np.float32)
-    levels = (alevel + blevel * np.float32(1000)).astype(np.float32)
-    yy, xx = torch.meshgrid(torch.linspace(0, 6.28, ny, device=dev), torch.linspace(0, 12.56, nx, device=dev), indexing="ij")
-    ps = (780 + 260 * torch.sin(xx) * torch.cos(yy) + torch.randn((ny, nx), generator=gen, device=dev)).clamp(520, 1040).contiguous()
+    alevel, blevel, levels, ps, make_coord = bk.hybrid_atmosphere(nx, ny, nlev, dev, gen)
     all_fields = torch.randn((max(NFS), nlev, ny, nx), generator=gen, device=dev, dtype=torch.float32) * 3 + 250
-    coord = (torch.from_numpy(alevel).to(dev)[:, None, None] + torch.from_numpy(blevel).to(dev)[:, None, None] * ps[None]).contiguous()
+    coord = make_coord()
     out_all = torch.empty((max(NFS), nlev, ny, nx), device=dev, dtype=torch.float32)
     mag_all = torch.empty((max(NFS) // 2, nlev, ny, nx), device=dev, dtype=torch.float32)
     lines = []
@@ -104,16 +73,15 @@ def main():
                         else:
                             call = lambda method=method, magnitude=magnitude, out=out: ctx.vderiv_levels(fields, levels, method, magnitude, out=out)  # noqa: B023, E731
                         calls["vderiv %s, %s" % (method, wname)] = call
-                ms = kernel_ms_alternating(ctx, calls)
-                base = stats(ms["vinterp"])
+                _, ms = bk.alternate(ctx, calls, ROUNDS)
+                base = bk.stats(ms["vinterp"])
                 base_bytes = vinterp_bytes(nx, ny, nlev, nf, 1, kind != "field")
                 base_gbps = base_bytes / base["kernel_ms"] / 1e6
                 base_lo = base_bytes / (base["kernel_ms_min"] + base["kernel_ms_spread"]) / 1e6  # its slowest call
                 for name, ts in ms.items():
                     alg = base_bytes if name == "vinterp" else vderiv_bytes(nx, ny, nlev, nf, kind, name.split(", ")[1])
-                    r = {"call": name, "coordinate": kind, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **stats(ts), "algorithmic_bytes": alg}
-                    r["GBps"] = round(alg / r["kernel_ms"] / 1e6, 1)
-                    r["share_of_8TBps"] = round(r["GBps"] / PEAK_GBPS, 3)
+                    r = {"call": name, "coordinate": kind, "nx": nx, "ny": ny, "nlev": nlev, "nfields": nf, **bk.stats(ts), "algorithmic_bytes": alg}
+                    r["GBps"], r["share_of_8TBps"] = bk.rate(alg, r["kernel_ms"])
                     print(json.dumps(r), flush=True)
                     if name != "vinterp":
                         best = alg / r["kernel_ms_min"] / 1e6  # its fastest call

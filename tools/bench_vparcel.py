@@ -17,23 +17,16 @@ saturation table, which these soundings do not produce).
     python tools/bench_vparcel.py [--small]   -> one JSON line per call, then one summary line
 """
 import json
-import os
 import sys
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
+from mi_fieldcalc_amd import vcumul, vparcel
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-from mi_fieldcalc_amd import vcumul, vparcel  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 ROUNDS = 9
-PEAK_GBPS = 8000.0
 EWT = [.000034, .000089, .000220, .000517, .001155, .002472, .005080, .01005, .01921, .03553, .06356, .1111, .1891, .3139, .5088, .8070, 1.2540,
        1.9118, 2.8627, 4.2148, 6.1078, 8.7192, 12.272, 17.044, 23.373, 31.671, 42.430, 56.236, 73.777, 95.855, 123.40, 157.46, 199.26, 250.16,
        311.69, 385.56, 473.67, 578.09, 701.13, 845.28, 1013.25]  # MetConstants.h:57-59
@@ -46,35 +39,16 @@ def qsat(t, p):
     return 0.622 * (tab[l] + (tab[l + 1] - tab[l]) * (x - l)) / p
 
 
-def kernel_ms_alternating(ctx, calls):
-    for call in calls.values():
-        call()  # warm-up: code object, scratch
-    torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
-    for _ in range(ROUNDS):
-        for name, call in calls.items():
-            ctx.timing_begin()
-            call()
-            torch.cuda.synchronize()
-            ms[name].append(ctx.timing_end_ms())
-    return ms
-
-
-def stats(ts):
-    return {"kernel_ms": round(float(np.median(ts)), 4), "kernel_ms_min": round(min(ts), 4), "kernel_ms_spread": round(max(ts) - min(ts), 4)}
-
-
 def main():
-    nx, ny, nlev = (360, 180, 24) if "--small" in sys.argv else (NX, NY, NLEV)
+    nx, ny, nlev = bk.shape(sys.argv)
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2024)
     # top-down, the last level is the surface; the top near 240 hPa: the levels a parcel is lifted through -- above them the
     # coldest parcels leave the saturation table (-100 C), which ends a walk by rule 3
-    eta = np.linspace(0.63, 1, nlev) ** 3
-    alevel, blevel = (1000 * (eta - eta ** 2)).astype(np.float32), (eta ** 2).astype(np.float32)
+    alevel, blevel, _ = bk.hybrid_levels(np.linspace(0.63, 1, nlev) ** 3)
     yy, xx = torch.meshgrid(torch.linspace(0, 6.28, ny, device=dev), torch.linspace(0, 12.56, nx, device=dev), indexing="ij")
     ps = (900 + 120 * torch.sin(xx) * torch.cos(yy) + torch.randn((ny, nx), generator=gen, device=dev)).clamp(700, 1040).contiguous()
-    p = (torch.from_numpy(alevel).to(dev)[:, None, None] + torch.from_numpy(blevel).to(dev)[:, None, None] * ps[None]).contiguous()
+    p = bk.coordinate_batch(alevel, blevel, ps, dev)
     ts = 285 + 17 * torch.cos(yy) * torch.sin(0.5 * xx)
     lapse = 0.17 + 0.04 * torch.sin(3 * xx)
     t = torch.maximum(ts[None] * (p / ps[None]) ** lapse[None], torch.full_like(p, 212.0)).contiguous()
@@ -101,12 +75,12 @@ def main():
             "vcumul log": lambda: vcumul.vcumul_hlevels(ctx, t, ps, alevel, blevel, "log", "last", out=zout),
             "showalterIndex": lambda: ctx.showalterIndex(t500, t850, rh850, 500.0, 850.0, 1, out=sout),
         }
-        ms = kernel_ms_alternating(ctx, calls)
+        _, ms = bk.alternate(ctx, calls, ROUNDS)
         form = vparcel.last_vparcel_form(ctx)
         # what the walk did, from its results
         r = vparcel.vparcel_hlevels(ctx, t, ps, alevel, blevel, q_src, src_level=nlev - 1, from_="last", outputs=vparcel.VPARCEL_OUTPUTS, out=outs)
         undef = float(vparcel.UNDEF)
-        pb = torch.from_numpy(alevel).to(dev)[:, None, None] + torch.from_numpy(blevel).to(dev)[:, None, None] * ps[None]
+        pb = bk.coordinate_batch(alevel, blevel, ps, dev)
         walked = r["tparcel"] != undef
         adjusted = walked & (pb < torch.where(r["plcl"] != undef, r["plcl"], torch.zeros_like(r["plcl"]))[None])
         adjusted[nlev - 1] = False  # the source level itself is not stepped to
@@ -122,11 +96,10 @@ def main():
               "showalterIndex": 4 * 4 * t850.numel()}
     res = {}
     for name, tms in ms.items():
-        s = stats(tms)
+        s = bk.stats(tms)
         res[name] = s["kernel_ms"]
-        gbps = bytes_[name] / s["kernel_ms"] / 1e6
-        print(json.dumps({"call": name, "nx": nx, "ny": ny, "nlev": nlev, **s, "algorithmic_bytes": bytes_[name], "GBps": round(gbps, 1),
-                          "share_of_8TBps": round(gbps / PEAK_GBPS, 3)}), flush=True)
+        gbps, share = bk.rate(bytes_[name], s["kernel_ms"])
+        print(json.dumps({"call": name, "nx": nx, "ny": ny, "nlev": nlev, **s, "algorithmic_bytes": bytes_[name], "GBps": gbps, "share_of_8TBps": share}), flush=True)
     trip_ns = res["showalterIndex"] * 1e6 / (t850.numel() * 7.0)  # ns per cell and trip, the loop's own loads and store included
     thermo_ms = trip_ns * trips * cells * (nlev - 1) / 1e6
     summary.update({"showalter_ns_per_cell_trip": round(trip_ns, 5), "trips_times_showalter_price_ms": round(thermo_ms, 3), "vcumul_log_ms": res["vcumul log"],

@@ -18,54 +18,26 @@ coefficient planes once -- and the rate they give, as a share of 8 TB/s.
 import json
 import os
 import sys
-import time
 
+import benchkit as bk  # first: the path and the measurement build (mifc_timing_*)
 import numpy as np
+import torch
+from bench_hinterp import rotated_grid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-os.environ.setdefault("MIFC_LIB_PATH", os.path.join(ROOT, "mi-fieldcalc_amd", "libmifc_measure.so"))  # mifc_timing_*
+import mi_fieldcalc_amd as fc
 
-import torch  # noqa: E402
-
-import mi_fieldcalc_amd as fc  # noqa: E402
-from bench_hinterp import rotated_grid  # noqa: E402
-
-NX, NY, NLEV = 1440, 720, 137
 ROUNDS = 9
-PEAK_TBPS = 8.0
 ADD, SUB, MUL = 1, 2, 3
-
-
-def time_alternating(ctx, calls, rounds=ROUNDS):
-    """calls: name -> (callable, one library call?).  One warm-up each, then `rounds` rounds in which every call is timed once, in turn."""
-    for call, _ in calls.values():
-        call()
-    torch.cuda.synchronize()
-    wall, kernel = {name: [] for name in calls}, {name: [] for name in calls}
-    for _ in range(rounds):
-        for name, (call, single) in calls.items():
-            torch.cuda.synchronize()
-            if single:
-                ctx.timing_begin()
-            t0 = time.perf_counter()
-            call()
-            torch.cuda.synchronize()
-            wall[name].append((time.perf_counter() - t0) * 1e3)
-            if single:
-                kernel[name].append(ctx.timing_end_ms())
-    return wall, kernel
+SINGLE, SEVERAL = bk.WALL_KERNEL, bk.WALL  # one timing section holds the call's launches, or the wall time alone
 
 
 def report(case, name, wall, kernel, nbytes, **more):
-    r = {"case": case, "call": name, "wall_ms": round(float(np.median(wall)), 4), "wall_ms_min": round(min(wall), 4),
-         "wall_ms_spread": round(max(wall) - min(wall), 4), **more}
+    r = {"case": case, "call": name, **bk.stats(wall, "wall_ms"), **more}
     if kernel:
-        r.update(kernel_ms=round(float(np.median(kernel)), 4), kernel_ms_min=round(min(kernel), 4), kernel_ms_spread=round(max(kernel) - min(kernel), 4))
+        r.update(bk.stats(kernel))
     if nbytes:
-        ms = r.get("kernel_ms", r["wall_ms"])
-        r.update(algorithmic_bytes=nbytes, TBps=round(nbytes / ms / 1e9, 3), share_of_peak=round(nbytes / ms / 1e9 / PEAK_TBPS, 3))
+        gbps, share = bk.rate(nbytes, r.get("kernel_ms", r["wall_ms"]))
+        r.update(algorithmic_bytes=nbytes, TBps=round(gbps / 1e3, 3), share_of_peak=share)
     print(json.dumps(r), flush=True)
     return r
 
@@ -93,18 +65,18 @@ def case_rotate(ctx, pairs, c, s, out):
         if np_ > npairs:
             break
         calls = {
-            "vrotate_levels": (lambda n=np_: ctx.vrotate_levels(pairs[:n], c, s, out=out[:n]), True),
-            "vrotate_levels, ALL_DEFINED": (lambda n=np_: ctx.vrotate_levels(pairs[:n], c, s, fdefined_in=every[:n], fdef_rot=fc.ALL_DEFINED, out=out[:n]), True),
+            "vrotate_levels": (lambda n=np_: ctx.vrotate_levels(pairs[:n], c, s, out=out[:n]), SINGLE),
+            "vrotate_levels, ALL_DEFINED": (lambda n=np_: ctx.vrotate_levels(pairs[:n], c, s, fdefined_in=every[:n], fdef_rot=fc.ALL_DEFINED, out=out[:n]), SINGLE),
         }
         if np_ == 1:
             u, v = pairs[0, 0], pairs[0, 1]
             tmp = torch.empty((2, ny, nx), device=u.device, dtype=torch.float32)
             ps = torch.full((ny, nx), 1000.0, device=u.device, dtype=torch.float32)
             yard = {"ff": out[0, 0], "dd": out[0, 1]}
-            calls["derived batch ff + dd (16 B per cell)"] = (lambda: ctx.hlevel_derived_batch(u, v, None, None, ps, None, None, ff=True, dd=True, out=yard), True)
-            calls["derived batch ff (12 B per cell)"] = (lambda: ctx.hlevel_derived_batch(u, v, None, None, ps, None, None, ff=True, out={"ff": out[0, 0]}), True)
-            calls["field algebra, 6 calls per level"] = (lambda: algebra(ctx, u, v, c, s, out[0, 0], out[0, 1], tmp), False)
-        wall, kernel = time_alternating(ctx, calls)
+            calls["derived batch ff + dd (16 B per cell)"] = (lambda: ctx.hlevel_derived_batch(u, v, None, None, ps, None, None, ff=True, dd=True, out=yard), SINGLE)
+            calls["derived batch ff (12 B per cell)"] = (lambda: ctx.hlevel_derived_batch(u, v, None, None, ps, None, None, ff=True, out={"ff": out[0, 0]}), SINGLE)
+            calls["field algebra, 6 calls per level"] = (lambda: algebra(ctx, u, v, c, s, out[0, 0], out[0, 1], tmp), SEVERAL)
+        wall, kernel = bk.alternate(ctx, calls, ROUNDS)
         res = {}
         for name in calls:
             nbytes = (12 if "12 B" in name else 16) * nlev * cells if name.startswith("derived") else (
@@ -131,8 +103,8 @@ def case_chunks(ctx, pairs, c, s, out, label):
         ctx.vrotate_levels(pairs[:1], c, s, out=out[:1])
 
     for chunk in order:
-        calls["chunk %s" % chunk] = (lambda chunk=chunk: forced(chunk), True)
-    wall, kernel = time_alternating(ctx, calls)
+        calls["chunk %s" % chunk] = (lambda chunk=chunk: forced(chunk), SINGLE)
+    wall, kernel = bk.alternate(ctx, calls, ROUNDS)
     for chunk in order:
         forced(chunk)
         report("chunks " + label, "chunk %s" % chunk, wall["chunk %s" % chunk], kernel["chunk %s" % chunk], rotate_bytes(1, nlev, ny * nx), nx=nx, ny=ny,
@@ -153,9 +125,9 @@ def case_sample(ctx, case, pair, x, y, c, s):
 
     calls = {}
     for method in ("bilinear", "bicubic"):
-        calls["hinterp_vector_levels %s" % method] = (lambda m=method: ctx.hinterp_vector_levels(pair, x, y, c, s, m, out=fused), True)
-        calls["hinterp_levels + vrotate_levels %s" % method] = (lambda m=method: two_calls(m), True)
-    wall, kernel = time_alternating(ctx, calls)
+        calls["hinterp_vector_levels %s" % method] = (lambda m=method: ctx.hinterp_vector_levels(pair, x, y, c, s, m, out=fused), SINGLE)
+        calls["hinterp_levels + vrotate_levels %s" % method] = (lambda m=method: two_calls(m), SINGLE)
+    wall, kernel = bk.alternate(ctx, calls, ROUNDS)
     res = {name: report(case, name, wall[name], kernel[name], 0, nx=nx, ny=ny, nlev=nlev, npos=npos) for name in calls}
     for method in ("bilinear", "bicubic"):
         one, two = res["hinterp_vector_levels %s" % method], res["hinterp_levels + vrotate_levels %s" % method]
@@ -165,9 +137,8 @@ def case_sample(ctx, case, pair, x, y, c, s):
 
 
 def main():
-    small = "--small" in sys.argv
-    nx, ny, nlev = (360, 180, 24) if small else (NX, NY, NLEV)
-    gx, gy, npts, npairs = (500, 250, 500, 2) if small else (2000, 1000, 2000, 4)
+    nx, ny, nlev = bk.shape(sys.argv)
+    gx, gy, npts, npairs, q = bk.shape(sys.argv, (2000, 1000, 2000, 4, 4), (500, 250, 500, 2, 2))
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(2026)
     with fc.Context(0) as ctx:
@@ -178,7 +149,6 @@ def main():
         c, s = torch.cos(angle).contiguous(), torch.sin(angle).contiguous()
         case_rotate(ctx, pairs, c, s, out)
         case_chunks(ctx, pairs, c, s, out, "%dx%d" % (nx, ny))
-        q = 4 if not small else 2
         case_chunks(ctx, pairs[:, :, :, :ny // q, :nx // q].contiguous(), c[:ny // q, :nx // q].contiguous(), s[:ny // q, :nx // q].contiguous(),
                     out[:, :, :, :ny // q, :nx // q].contiguous(), "%dx%d" % (nx // q, ny // q))
         case_chunks(ctx, pairs[:, :, :, :ny // (4 * q), :nx // (4 * q)].contiguous(), c[:ny // (4 * q), :nx // (4 * q)].contiguous(),
