@@ -963,6 +963,70 @@ int mifc_hremap_levels(mifc_ctx* ctx, const mifc_hremap_plan* plan, int nx, int 
                        float* const* fres, int* fdefined_out, float undef, int memkind);
 const char* mifc_last_hremap_form(void);
 
+/* ---- EXTENSION: field expressions over level batches, a register program per cell in one pass ------------------
+ * Not a miutil::fieldcalc function.  Field algebra (fieldOPERfield, fieldOPERconstant, constantOPERfield, min/maxvalueField*,
+ * abs/log/log10/exp/pow10/powerField) is what callers compose everything with that has no named operator, one field and
+ * one operation at a time: a launch and 12 B per cell per operation, every intermediate through memory.  mifc_fexpr_levels
+ * evaluates a small register program per cell over level batches in one launch, 4 * (inputs + outputs) bytes per cell.
+ * Every operation is rounded exactly as the single-field entry rounds it, so a program made of those operations gives the
+ * bits of the chain of calls it replaces (called with SOME_DEFINED flags).
+ *   1. Registers.  A cell has MIFC_FEXPR_NREGS = 16 float registers.  Registers 0 .. nfields - 1 start as the cell's value
+ *      of fields[f] at this level, the next nplanes registers as the cell's value of planes[p] (the same plane at every
+ *      level); the others are unset.  nfields 0..8, nplanes 0..4, nfields + nplanes 1..12.  A program may overwrite input
+ *      registers.
+ *   2. Instructions.  mifc_fexpr_ins {op, dst, a, b, c}: dst is a register; a source byte is a register (0..15),
+ *      MIFC_FEXPR_LEVEL(s), row s of level_scalars (float[nscalars][nlev], nscalars <= 4) at this level, or
+ *      MIFC_FEXPR_CONST(j), consts[j] (nconsts <= 16).  Source bytes an operation does not read (b of a one-operand
+ *      operation, c of all but SELECT and MASK) and pad are ignored.  ncode 1..64.
+ *   3. Operations, one float result each, every one rounded on its own, nothing contracted:
+ *        ADD SUB MUL       a op b
+ *        DIV               a / b, undef where b == 0 (divideUndef, FieldCalculations.cc:84)
+ *        MIN, MAX          b < a ? b : a,  a < b ? b : a (std::min / std::max of minvalueFields, maxvalueFields)
+ *        ABS NEG SQRT      of a; SQRT is the correctly rounded float square root
+ *        LOG LOG10 EXP POW10   of a, the functions of mifc_logField, mifc_log10Field, mifc_expField, mifc_pow10Field
+ *        POW               a ^ b, the function of mifc_powerField (b any operand)
+ *        LT LE EQ NE       a op b: 1.0f or 0.0f
+ *        MOV               a
+ *        SELECT            c != 0 ? a : b; it reads c and the chosen operand only
+ *        IFDEF             a where a is defined, else b as it is (b is not tested)
+ *        MASK              a as it is where c is defined and c != 0, else undef (a is not tested)
+ *   4. Undefined.  There is no defined bit: a register holds undef as a value, and "x is defined" is the library's test
+ *      everywhere, !isnan(x) && x != undef.  Except for IFDEF and MASK as said in 3, the result of an operation is undef
+ *      if an operand it reads is not defined; otherwise it is the arithmetic result, which may itself be NaN, infinite or
+ *      == undef (the next operation then finds it undefined, as a chain of single-field calls would).  Input flags are
+ *      not taken: every operand is always tested.
+ *   5. Outputs.  fres[o] receives register out_regs[o], o < nout (1..4), after the last instruction.
+ *      fdefined_out[o * nlev + k] = checkDefined(cells of output o at level k with value == undef, nx * ny); a NaN is not
+ *      counted, as everywhere else.
+ *   6. Refused, with 0, nothing written and the reason in mifc_last_error(): an open mifc_graph capture; nlev < 1; counts
+ *      outside the limits of 1, 2 and 5; an unknown op; a register or operand index out of range; a register that is read,
+ *      by an instruction or by out_regs, before anything set it; a null pointer that is needed; negative nx or ny; more
+ *      than 2^31 - 1 cells per level; an unknown memkind; an output that overlaps a field, a plane or another output by
+ *      byte range (in place is not offered).  nx * ny == 0 succeeds and writes only flags (ALL_DEFINED).
+ * (Restated in numpy in tests/fexpr_restate.py; the program check is mi-fieldcalc_amd/csrc/mifc_fexpr_prog.h.)
+ * `fields`, `planes` and `fres` are HOST tables of pointers to memory of `memkind`; level_scalars, consts, code, out_regs
+ * and fdefined_out are HOST arrays.  Device memory is used where it is, with one synchronisation at the end: four cells
+ * per lane through 16-byte accesses where every pointer is on the 16-byte grid (a level size that is no multiple of four
+ * leaves up to three cells per level to a second, small launch), one cell per lane otherwise.  Host memory works at any
+ * size, a band of rows of every level at a time in MIFC_FEXPR_CHUNK_MIB of device memory (default 256).
+ * mifc_last_fexpr_form: the launch shape of the calling thread's last mifc_fexpr_levels call that launched, a diagnostic
+ * for tests: "family=fexpr form=vector|scalar grid=<grid.x> nlev=<grid.y> ncode=<n> nregs=<registers in use> nout=<n>
+ * tail=<cells per level of the tail launch> partials=0 tables=0|1 bands=<problems launched>"; "" before the first. */
+enum { MIFC_FEXPR_ADD = 0, MIFC_FEXPR_SUB = 1, MIFC_FEXPR_MUL = 2, MIFC_FEXPR_DIV = 3, MIFC_FEXPR_MIN = 4, MIFC_FEXPR_MAX = 5,
+       MIFC_FEXPR_ABS = 6, MIFC_FEXPR_NEG = 7, MIFC_FEXPR_SQRT = 8, MIFC_FEXPR_LOG = 9, MIFC_FEXPR_LOG10 = 10, MIFC_FEXPR_EXP = 11,
+       MIFC_FEXPR_POW10 = 12, MIFC_FEXPR_POW = 13, MIFC_FEXPR_LT = 14, MIFC_FEXPR_LE = 15, MIFC_FEXPR_EQ = 16, MIFC_FEXPR_NE = 17,
+       MIFC_FEXPR_SELECT = 18, MIFC_FEXPR_IFDEF = 19, MIFC_FEXPR_MASK = 20, MIFC_FEXPR_MOV = 21, MIFC_FEXPR_NOPS = 22 };
+enum { MIFC_FEXPR_NREGS = 16, MIFC_FEXPR_MAX_FIELDS = 8, MIFC_FEXPR_MAX_PLANES = 4, MIFC_FEXPR_MAX_INPUTS = 12, MIFC_FEXPR_MAX_SCALARS = 4,
+       MIFC_FEXPR_MAX_CONSTS = 16, MIFC_FEXPR_MAX_CODE = 64, MIFC_FEXPR_MAX_OUT = 4 };
+#define MIFC_FEXPR_LEVEL(s) (16 + (s))
+#define MIFC_FEXPR_CONST(j) (32 + (j))
+typedef struct { unsigned char op, dst, a, b, c, pad[3]; } mifc_fexpr_ins; /* 8 bytes */
+int mifc_fexpr_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, int nfields, const float* const* planes,
+                      int nplanes, const float* level_scalars, int nscalars, const float* consts, int nconsts,
+                      const mifc_fexpr_ins* code, int ncode, const int* out_regs, int nout, float* const* fres,
+                      int* fdefined_out, float undef, int memkind);
+const char* mifc_last_fexpr_form(void);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

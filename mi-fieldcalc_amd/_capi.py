@@ -168,6 +168,9 @@ SIGNATURES = {
     "mifc_hremap_plan_info": ("i", ["p", "p", "pi", "pi"]),
     "mifc_hremap_levels": ("i", ["ctx", "p", "i", "i", "i", "p", "pi", "i", "i", "d", "p", "pi", "f", "i"]),
     "mifc_last_hremap_form": ("s", []),
+    # EXTENSION: a register program per cell over level batches (fields, planes, fres: host tables of pointers; the rest host arrays)
+    "mifc_fexpr_levels": ("i", ["ctx", "i", "i", "i", "p", "i", "p", "i", "p", "i", "p", "i", "p", "i", "pi", "i", "p", "pi", "f", "i"]),
+    "mifc_last_fexpr_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

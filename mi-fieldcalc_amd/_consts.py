@@ -25,3 +25,8 @@ HINTERP_METHODS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 # the modes and product groups of mifc_hstats_levels (MIFC_HSTATS_*)
 HSTATS_MODES = {"area": 0, "rows": 1}
 HSTATS_PRODUCTS = {"moments": 1, "extremes": 2}
+# the operations of mifc_fexpr_levels (MIFC_FEXPR_*, in enum order), where its operand bytes begin and its limits
+FEXPR_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3, "min": 4, "max": 5, "abs": 6, "neg": 7, "sqrt": 8, "log": 9, "log10": 10, "exp": 11, "pow10": 12,
+             "pow": 13, "lt": 14, "le": 15, "eq": 16, "ne": 17, "select": 18, "ifdef": 19, "mask": 20, "mov": 21}
+FEXPR_LEVEL0, FEXPR_CONST0 = 16, 32
+FEXPR_LIMITS = {"nregs": 16, "fields": 8, "planes": 4, "inputs": 12, "scalars": 4, "consts": 16, "code": 64, "out": 4}

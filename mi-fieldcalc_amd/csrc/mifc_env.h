@@ -33,6 +33,7 @@ struct Env
   int hinterp_chunk_mib = 0;      // MIFC_HINTERP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hinterp_levels call, whole levels at a time (default 256); mifc_hinterp_vector_levels too
   int hstats_chunk_mib = 0;       // MIFC_HSTATS_CHUNK_MIB (> 0): device staging of a host-memory mifc_hstats_levels call, a band of rows at a time (default 256)
   int hremap_chunk_mib = 0;       // MIFC_HREMAP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hremap_levels call, whole levels at a time (default 256)
+  int fexpr_chunk_mib = 0;        // MIFC_FEXPR_CHUNK_MIB (> 0): device staging of a host-memory mifc_fexpr_levels call, a band of rows at a time (default 256)
   int hremap_level_chunk = 0;     // MIFC_HREMAP_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the hremap kernel takes; A/B, tests)
   int hinterp_level_chunk = 0;    // MIFC_HINTERP_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the hinterp and vrotate kernels walks; A/B, tests)
   int derived_blocks = 0;         // MIFC_DERIVED_BLOCKS (> 0 overrides the persistent grid of the fused derived kernel)

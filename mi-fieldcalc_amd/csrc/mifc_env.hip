@@ -62,6 +62,7 @@ void env_reload()
   e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
   e.hremap_chunk_mib = positive_int("MIFC_HREMAP_CHUNK_MIB");
   e.hremap_level_chunk = positive_int("MIFC_HREMAP_LEVEL_CHUNK");
+  e.fexpr_chunk_mib = positive_int("MIFC_FEXPR_CHUNK_MIB");
   e.hinterp_level_chunk = positive_int("MIFC_HINTERP_LEVEL_CHUNK");
   e.derived_blocks = positive_int("MIFC_DERIVED_BLOCKS");
   e.derived_pipe = not_zero("MIFC_DERIVED_PIPE") ? 1 : 0;

@@ -687,6 +687,39 @@ struct VrotatePlan
 VrotatePlan vrotate_plan(int cells, int nlev, int vec4 = 1);
 hipError_t launch_vrotate(const VrotateParams& prm, hipStream_t stream);
 
+// ------------------------------------ field expressions over level batches (mifc_fexpr.hip), EXTENSION
+// One launch per problem evaluates the register program of mifc_fexpr_levels (include/mifc.h, rules 1-5) in every cell:
+// grid.y is the level, a lane owns four consecutive cells (16-byte accesses) or one.  The program, its constants and the
+// pointers travel in the kernel arguments; `code` is the program as mifc_fexpr_prog.h normalised it (op | dst << 8 |
+// a << 16 | b << 24, then c), so the instruction words are scalar loads.  Input i < nfields is a batch (level k at
+// in[i] + k * stride), the next nplanes are planes; out[o] receives register (out_regs >> 8 o) & 255.  The launch covers
+// the cells cell0 .. cell0 + n - 1 of the levels lev0 .. lev0 + grid.y - 1; level_scalars is float[..][nlev_all] on the
+// device, the counters n_undefined[o * nlev_all + k] are zeroed by the caller.
+const int FEXPR_MAX_IN = 12, FEXPR_MAX_OUT = 4, FEXPR_MAX_CODE = 64, FEXPR_MAX_CONSTS = 16;
+struct FexprParams
+{
+  int n, lev0, nlev_all;
+  int ncode, nfields, nplanes, nout;
+  unsigned int out_regs;
+  float undef;
+  long stride, cell0;
+  const float* in[FEXPR_MAX_IN];
+  float* out[FEXPR_MAX_OUT];
+  const float* level_scalars;
+  u64* n_undefined;
+  unsigned int code[2 * FEXPR_MAX_CODE];
+  float consts[FEXPR_MAX_CONSTS];
+};
+// The launch shape, the one rule for it: the vector form where every pointer of the call is on the 16-byte grid and a level
+// has four cells or more -- ceil(n / 4 / 256) workgroups per level, and the n % 4 cells a level has left go to one
+// 64-lane workgroup per level of the scalar kernel --, else the scalar form, ceil(n / 256) workgroups per level.
+struct FexprShape
+{
+  int vector, grid, tail;
+};
+FexprShape fexpr_shape(const FexprParams& prm);
+hipError_t launch_fexpr(const FexprParams& prm, int nlev, int tables, hipStream_t stream);
+
 // ------------------------------------ horizontal statistics of level batches (mifc_hstats.hip), EXTENSION
 // Two kernels (rules 1-7 of mifc_hstats_levels, include/mifc.h).  The segment kernel: a wave owns one (row, segment) of up
 // to HSTATS_PASS fields -- the columns [4096 s, 4096 s + 4096) of one grid row, cut to the box -- and walks the levels
