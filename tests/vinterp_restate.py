@@ -31,9 +31,11 @@ def hybrid_coordinate(ps, alevel, blevel):
         return np.stack([(a[k] + (b[k] * ps).astype(np.float32)).astype(np.float32) for k in range(a.size)])
 
 
-def interpolate(fields, coord, coord_defined, targets, method, flags=None, undef=UNDEF):
+def interpolate(fields, coord, coord_defined, targets, method, flags=None, undef=UNDEF, prefilter=None):
     """fields float32 (nf, nlev, ny, nx); coord float32 (nlev, ny, nx) and coord_defined bool of the same shape (rule 1);
-    flags None (SOME_DEFINED) or (nf, nlev).  Returns (out (nf, nt, ny, nx), flags_out int32 (nf, nt))."""
+    flags None (SOME_DEFINED) or (nf, nlev).  Returns (out (nf, nt, ny, nx), flags_out int32 (nf, nt)).  prefilter: not part
+    of the definition -- a test's model of a filter in front of the bracket test, called as prefilter(k, t) and giving per
+    cell whether the pair (k, k + 1) is looked at for target t at all."""
     x = np.asarray(fields, np.float32)
     nf, nlev, ny, nx = x.shape
     cells = ny * nx
@@ -52,6 +54,8 @@ def interpolate(fields, coord, coord_defined, targets, method, flags=None, undef
                 ck, ck1 = c[k], c[k + 1]
                 lo, hi = np.minimum(ck, ck1), np.maximum(ck, ck1)  # a NaN comes through and fails both comparisons
                 br = cdef[k] & cdef[k + 1] & (lo <= ct) & (ct <= hi) & ~found
+                if prefilter is not None:
+                    br &= prefilter(k, t)
                 if not br.any():
                     continue
                 found |= br
@@ -75,17 +79,17 @@ def interpolate(fields, coord, coord_defined, targets, method, flags=None, undef
     return out.reshape(nf, tg.size, ny, nx), fd
 
 
-def hlevels(fields, ps, alevel, blevel, targets, method, flags=None, fdef_ps=SOME_DEFINED, undef=UNDEF):
+def hlevels(fields, ps, alevel, blevel, targets, method, flags=None, fdef_ps=SOME_DEFINED, undef=UNDEF, prefilter=None):
     c = hybrid_coordinate(ps, alevel, blevel)
     psd = is_defined(fdef_ps == ALL_DEFINED, np.asarray(ps, np.float32), undef)
-    return interpolate(fields, c, np.broadcast_to(psd, c.shape), targets, method, flags, undef)
+    return interpolate(fields, c, np.broadcast_to(psd, c.shape), targets, method, flags, undef, prefilter)
 
 
-def coord_fields(fields, coord, targets, method, flags=None, fdef_coord=None, undef=UNDEF):
+def coord_fields(fields, coord, targets, method, flags=None, fdef_coord=None, undef=UNDEF, prefilter=None):
     c = np.asarray(coord, np.float32)
     fc = [SOME_DEFINED] * c.shape[0] if fdef_coord is None else list(fdef_coord)
     cdef = np.stack([is_defined(fc[k] == ALL_DEFINED, c[k], undef) for k in range(c.shape[0])])
-    return interpolate(fields, c, cdef, targets, method, flags, undef)
+    return interpolate(fields, c, cdef, targets, method, flags, undef, prefilter)
 
 
 # ---------------------------------------------------------------------------------------------- case generators
