@@ -817,7 +817,10 @@ const char* mifc_last_hinterp_form(void);
  * batches with the flags of the first call and the coefficients as a (1, npos) plane.  A component is undefined (R2) where
  * rules 1, 4 and 5 left a hole.  The one call carries these holes, the second of two calls can only recognise them by
  * their value: the two differ where a component flagged ALL_DEFINED stores undef or NaN all the same -- the sampling hands
- * such a value on as the value it is (rule 3), this call rotates it, two calls take it for a hole.  A point whose
+ * such a value on as the value it is (rule 3), this call rotates it, two calls take it for a hole.  The same holds for a
+ * sampled value that the arithmetic made NaN or bit-equal to undef (inf - inf between two corners; the midpoint of 0 and
+ * 2e35f): a computed result is a value (rule 7) and is rotated here, while the second of two calls, whose input flag is the
+ * first call's output flag, takes it for a hole wherever that flag is not ALL_DEFINED.  A point whose
  * coefficients are undefined is treated like an unusable position: undef for every pair and level, counted once.  The refusals are those
  * of mifc_hinterp_levels ("npairs <n> outside 1..4"; cosa and sina may not be null nor overlap an output); host memory is
  * staged in whole levels (MIFC_HINTERP_CHUNK_MIB).  The call reports through mifc_last_hinterp_form, nf = the components

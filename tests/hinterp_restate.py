@@ -22,10 +22,19 @@ def cubic_weights(t):
     return [((-0.5 * t + 1.0) * t - 0.5) * t, ((1.5 * t - 2.5) * t) * t + 1.0, ((-1.5 * t + 2.0) * t + 0.5) * t, ((0.5 * t - 0.5) * t) * t]
 
 
-def sample(fields, xpos, ypos, method=BILINEAR, flags=None, undef=UNDEF, branches=None):
+# Departures from the definition that a test may ask for by name (`mistakes`): what a kernel that is subtly wrong would
+# compute.  tests/test_horizontal_range_cpu.py shows that the cases of tests/horizontal_range_cases.py tell each from the rules.
+MISTAKES = ("no select", "nearest in float", "no cubic on rows", "undef after the fact")
+
+
+def sample(fields, xpos, ypos, method=BILINEAR, flags=None, undef=UNDEF, branches=None, mistakes=(), cells=None):
     """fields float32 (nf, nlev, ny, nx); xpos, ypos float32 of one shape S; flags None (SOME_DEFINED) or (nf, nlev).
     Returns (out (nf, nlev) + S, flags_out int32 (nf, nlev)).  branches: an int array like out that receives the branch of
-    every output."""
+    every output.  cells: a dict that receives rule 2 per point (i0, j0, a, b, usable).  mistakes: not part of the
+    definition -- names from MISTAKES: "no select" reads column i0 + 1 and row j0 + 1 always (clamped to the grid) and
+    adds a * (x10 - x00) and b * (r1 - r0) whether or not a, b are zero; "nearest in float" adds the 0.5 of rule 4 in float;
+    "no cubic on rows" leaves rule 6 out where b == 0; "undef after the fact" takes a result equal to undef for a hole."""
+    assert all(m in MISTAKES for m in mistakes), mistakes
     f = np.asarray(fields, np.float32)
     nf, nlev, ny, nx = f.shape
     xp, yp = np.asarray(xpos, np.float32), np.asarray(ypos, np.float32)
@@ -53,6 +62,18 @@ def sample(fields, xpos, ypos, method=BILINEAR, flags=None, undef=UNDEF, branche
         i1, j1 = i0 + ~a0, j0 + ~b0  # read only where needed: elsewhere the same column / row again
         inear, jnear = (xs + 0.5).astype(np.int64), (ys + 0.5).astype(np.int64)
         inside = ~(a0 & b0) & (i0 >= 1) & (i0 <= nx - 3) & (j0 >= 1) & (j0 <= ny - 3)
+        select_a, select_b = a0, b0
+        if "no select" in mistakes:
+            i1, j1 = np.minimum(i0 + 1, nx - 1), np.minimum(j0 + 1, ny - 1)
+            select_a, select_b = np.zeros_like(a0), np.zeros_like(b0)
+        if "nearest in float" in mistakes:
+            half = np.float32(0.5)
+            inear, jnear = (xs.astype(np.float32) + half).astype(np.int64), (ys.astype(np.float32) + half).astype(np.int64)
+            inear, jnear = np.minimum(inear, nx - 1), np.minimum(jnear, ny - 1)
+        if "no cubic on rows" in mistakes:
+            inside = inside & ~b0
+        if cells is not None:
+            cells.update(i0=i0, j0=j0, a=a, b=b, usable=usable)
         ci = [np.clip(i0 + n, 0, nx - 1) for n in (-1, 0, 1, 2)]  # (clipped only where the cubic rule does not apply)
         cj = [np.clip(j0 + m, 0, ny - 1) for m in (-1, 0, 1, 2)]
         wx, wy = cubic_weights(a), cubic_weights(b)
@@ -70,9 +91,9 @@ def sample(fields, xpos, ypos, method=BILINEAR, flags=None, undef=UNDEF, branche
                     d00, d10, d01, d11 = (is_defined(all_defined, v, undef) for v in (v00, v10, v01, v11))
                     ok = d00 & (a0 | d10) & (b0 | d01) & (a0 | b0 | d11)
                     x00, x10, x01, x11 = (v.astype(np.float64) for v in (v00, v10, v01, v11))
-                    r0 = np.where(a0, x00, x00 + a * (x10 - x00))
-                    r1 = np.where(a0, x01, x01 + a * (x11 - x01))
-                    res = np.where(b0, r0, r0 + b * (r1 - r0)).astype(np.float32)
+                    r0 = np.where(select_a, x00, x00 + a * (x10 - x00))
+                    r1 = np.where(select_a, x01, x01 + a * (x11 - x01))
+                    res = np.where(select_b, r0, r0 + b * (r1 - r0)).astype(np.float32)
                     branch = np.where(ok, np.where(b0, ON_ROW, FULL_BILINEAR), BILINEAR_UNDEFINED)
                     if method == BICUBIC:  # rule 6
                         block = [[lev[cj[m], ci[n]] for n in range(4)] for m in range(4)]
@@ -87,6 +108,8 @@ def sample(fields, xpos, ypos, method=BILINEAR, flags=None, undef=UNDEF, branche
                         ok = ok | cubic
                         branch = np.where(cubic, CUBIC, branch)
                 bad = ~usable | ~ok
+                if "undef after the fact" in mistakes:
+                    bad = bad | (res == undef)
                 out[g, k] = np.where(bad, undef, res)
                 br[g, k] = np.where(~pos_defined, POSITION_UNDEFINED, np.where(~usable, OUTSIDE, branch))
                 fd[g, k] = classify(int(bad.sum()), npos)  # rule 7

@@ -24,9 +24,29 @@ def row_sums(rowptr, w):
     return wall
 
 
-def remap(fields, rowptr, col, w, mode=STRICT, min_frac=0.0, flags=None, undef=UNDEF):
+# Departures from the definition that a test may ask for by name (`mistakes`): what a kernel that is subtly wrong would
+# compute.  tests/test_horizontal_range_cpu.py shows that the cases of tests/horizontal_range_cases.py tell each from the rules.
+MISTAKES = ("padding added as zero", "greater in place of greater or equal", "undef after the fact")
+SLICE = 64  # destinations of a slice of the plan's layout: its rows are padded to the longest of them
+
+
+def padding_columns(rowptr, col):
+    """The source cell that the padding entries of each row name in the plan's layout (mifc_hremap_plan.h): the row's first
+    column, 0 for an empty row; and the width of each row's slice."""
+    rowptr, col = np.asarray(rowptr, np.int64), np.asarray(col, np.int64)
+    length = np.diff(rowptr)
+    first = np.where(length > 0, col[np.minimum(rowptr[:-1], max(col.size - 1, 0))] if col.size else 0, 0)
+    width = np.concatenate([np.full(length[s:s + SLICE].size, length[s:s + SLICE].max()) for s in range(0, length.size, SLICE)])
+    return first, width
+
+
+def remap(fields, rowptr, col, w, mode=STRICT, min_frac=0.0, flags=None, undef=UNDEF, mistakes=()):
     """fields float32 (nf, nlev, ny, nx) or (nf, nlev, nsrc); the table in CSR form; flags None (SOME_DEFINED) or
-    (nf, nlev).  Returns (out float32 (nf, nlev, ndst), flags_out int32 (nf, nlev))."""
+    (nf, nlev).  Returns (out float32 (nf, nlev, ndst), flags_out int32 (nf, nlev)).  mistakes: not part of the
+    definition -- names from MISTAKES: "padding added as zero" adds 0 * x of the padding cell for the trips between a row's
+    end and the width of its slice; "greater in place of greater or equal" in the min_frac test; "undef after the fact"
+    takes a result equal to undef for a hole."""
+    assert all(m in MISTAKES for m in mistakes), mistakes
     f = np.asarray(fields, np.float32)
     nf, nlev = f.shape[:2]
     f = f.reshape(nf, nlev, -1)
@@ -52,9 +72,15 @@ def remap(fields, rowptr, col, w, mode=STRICT, min_frac=0.0, flags=None, undef=U
                     e = np.where(active, rowptr[:-1] + r, 0)
                     c = col[e] if col.size else np.zeros(ndst, np.int64)
                     we = (w[e] if w.size else np.zeros(ndst, np.float32)).astype(np.float64)
+                    if "padding added as zero" in mistakes:
+                        pad_col, width = padding_columns(rowptr, col)
+                        padding = ~active & (r < width)
+                        c, we = np.where(padding, pad_col, c), np.where(padding, 0.0, we)
                     x = lev[c]
                     ok = is_defined(all_defined, x, undef)
                     use = active & ok
+                    if "padding added as zero" in mistakes:
+                        use = use | padding  # (the sums only: such an entry is not counted as bad)
                     prod = we * x.astype(np.float64)
                     S = np.where(use, S + prod, S)
                     wdef = np.where(use, wdef + we, wdef)
@@ -64,9 +90,12 @@ def remap(fields, rowptr, col, w, mode=STRICT, min_frac=0.0, flags=None, undef=U
                     hole = (length == 0) | (nbad > 0)
                     res = plain
                 else:
-                    lost = (nbad == length) | (wdef == 0.0) | ~(np.abs(wdef) >= np.float64(min_frac) * np.abs(wall))
+                    enough = np.greater if "greater in place of greater or equal" in mistakes else np.greater_equal
+                    lost = (nbad == length) | (wdef == 0.0) | ~enough(np.abs(wdef), np.float64(min_frac) * np.abs(wall))
                     hole = (length == 0) | ((nbad > 0) & lost)
                     res = np.where(nbad > 0, ((S / wdef) * wall).astype(np.float32), plain)
+                if "undef after the fact" in mistakes:
+                    hole = hole | (res == undef)
                 out[g, k] = np.where(hole, undef, res)
                 fd[g, k] = classify(int(hole.sum()), ndst)
     return out, fd

@@ -25,9 +25,20 @@ def _flags(flags, nf, nlev):
     return np.full((nf, nlev), SOME_DEFINED) if flags is None else np.asarray(flags).reshape(nf, nlev)
 
 
-def cell_quantities(x, flag, y, flag_y, pivot, weight, fdef_weight, box, undef=UNDEF):
+# Departures from the definition that a test may ask for by name (`mistakes`): what a kernel that is subtly wrong would
+# compute.  tests/test_horizontal_range_cpu.py shows that the cases of tests/horizontal_range_cases.py tell each from the rules.
+MISTAKES = ("masked by multiplication", "doubles flushed", "undef after the fact")
+
+
+def flushed64(a):
+    """Subnormal doubles replaced by zeros of their sign."""
+    with np.errstate(invalid="ignore"):
+        return np.where((a != 0) & (np.abs(a) < np.finfo(np.float64).tiny), np.copysign(0.0, a), a)
+
+
+def cell_quantities(x, flag, y, flag_y, pivot, weight, fdef_weight, box, undef=UNDEF, mistakes=()):
     """Rules 1 and 2 for one level x (ny, nx): (included, d, w, q1, q2) over the whole level, float64; excluded cells
-    carry w = q1 = q2 = +0.0 (d is whatever it is there)."""
+    carry w = q1 = q2 = +0.0 (d is whatever it is there).  mistakes: see hstats()."""
     undef = np.float32(undef)
     ny, nx = x.shape
     i0, i1, j0, j1 = box
@@ -45,8 +56,17 @@ def cell_quantities(x, flag, y, flag_y, pivot, weight, fdef_weight, box, undef=U
             w = weight.astype(np.float64)
         else:
             w = np.ones((ny, nx))
+        if "doubles flushed" in mistakes:  # (a float widened to double is never a subnormal double: the pivot and the results are)
+            d = flushed64(x.astype(np.float64) - (0.0 if y is None else y.astype(np.float64)))
+            d = flushed64(d - flushed64(np.float64(pivot)))
         q1 = w * d
         q2 = q1 * d
+        if "doubles flushed" in mistakes:
+            q1 = flushed64(q1)
+            q2 = flushed64(q1 * d)
+        if "masked by multiplication" in mistakes:  # 0 * inf and 0 * NaN are NaN; 0 * -1 is -0.0
+            m = inc.astype(np.float64)
+            return inc, d, m * w, m * q1, m * q2
     zero = np.float64(0.0)
     return inc, d, np.where(inc, w, zero), np.where(inc, q1, zero), np.where(inc, q2, zero)
 
@@ -109,10 +129,14 @@ def extremes(inc, d, box, mode):
 
 
 def hstats(fields, minus=None, pivot=None, weight=None, box=None, mode=AREA, products=MOMENTS | EXTREMES, flags=None, flags_minus=None,
-           fdef_weight=SOME_DEFINED, undef=UNDEF, fill=0.0):
+           fdef_weight=SOME_DEFINED, undef=UNDEF, fill=0.0, mistakes=()):
     """fields float32 (nf, nlev, ny, nx); minus None or like fields; pivot None or (nf, nlev) float64; weight None or
     float32 (ny, nx); box None or (i0, i1, j0, j1).  Returns (stats float64 (nf, nlev, nrows, 8), mean float32
-    (nf, nlev, nrows), flags int32 (nf, nlev)); the slots of a group that is not in `products` hold `fill`."""
+    (nf, nlev, nrows), flags int32 (nf, nlev)); the slots of a group that is not in `products` hold `fill`.  mistakes: not
+    part of the definition -- names from MISTAKES: "masked by multiplication" multiplies w, q1 and q2 of every cell by 1.0
+    or 0.0 instead of selecting; "doubles flushed" takes every subnormal double of rule 2 for a zero; "undef after the
+    fact" takes a mean equal to undef for a hole."""
+    assert all(m in MISTAKES for m in mistakes), mistakes
     f = np.asarray(fields, np.float32)
     nf, nlev, ny, nx = f.shape
     mode = MODES.get(mode, mode)
@@ -128,7 +152,8 @@ def hstats(fields, minus=None, pivot=None, weight=None, box=None, mode=AREA, pro
     mean = np.full((nf, nlev, nrows), undef, np.float32)
     fd = np.zeros((nf, nlev), np.int32)
     for g in range(nf):
-        q = [cell_quantities(f[g, k], fl[g, k], None if y is None else y[g, k], flm[g, k], pv[g, k], wt, fdef_weight, bx, undef) for k in range(nlev)]
+        q = [cell_quantities(f[g, k], fl[g, k], None if y is None else y[g, k], flm[g, k], pv[g, k], wt, fdef_weight, bx, undef, mistakes)
+             for k in range(nlev)]
         inc, d = np.stack([c[0] for c in q]), np.stack([c[1] for c in q])
         if products & MOMENTS:
             count = inc[:, j0:j1].sum(axis=2).astype(np.float64)
@@ -138,6 +163,8 @@ def hstats(fields, minus=None, pivot=None, weight=None, box=None, mode=AREA, pro
             with np.errstate(all="ignore"):
                 value = (pv[g][:, None] + stats[g, :, :, S1] / stats[g, :, :, W]).astype(np.float32)
             hole = (stats[g, :, :, N] == 0) | (stats[g, :, :, W] == 0.0)
+            if "undef after the fact" in mistakes:
+                hole = hole | (value == undef)
             mean[g] = np.where(hole, undef, value)
             for k in range(nlev):
                 fd[g, k] = classify(int(hole[k].sum()), nrows)
