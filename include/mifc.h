@@ -888,7 +888,8 @@ int mifc_hinterp_vector_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const fl
  * result is the same): no copies, one synchronisation at the end.  Host memory works at any size: rows are independent up
  * to rule 4, so the call stages a band of rows of every level at a time, MIFC_HSTATS_CHUNK_MIB of device memory (default
  * 256), and combines the partial sums of all bands at the end -- bit for bit the result of one device call
- * (DESIGN.md 4.22).  Not offered: reduction along y only; histograms and percentiles over an area; products of two fields.
+ * (DESIGN.md 4.22).  Not offered: reduction along y only; products of two fields.  Histograms and percentiles over an area: the
+ * mifc_hdist_* entries below.
  * mifc_last_hstats_form: the launch shape of the calling thread's last mifc_hstats_levels call, a diagnostic for tests:
  * "mode=area|rows v=4|1 nf=<fields per launch> w=0|1 minus=0|1 tested=0|1 products=<mask> segs=<segments per row>
  * blocks=<grid.x> launches=<n> bands=<n>" (launches: of the segment kernel); "" before the first call. */
@@ -1029,6 +1030,66 @@ int mifc_fexpr_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* cons
                       const mifc_fexpr_ins* code, int ncode, const int* out_regs, int nout, float* const* fres,
                       int* fdefined_out, float undef, int memkind);
 const char* mifc_last_fexpr_form(void);
+
+/* ---- EXTENSION: area histograms and exact percentiles of level batches -----------------------------------------
+ * Not a miutil::fieldcalc function.  mifc_hstats_levels stops at counts, sums and extremes; a robust colour scale (the 2 %
+ * and 98 % of a level), the area fraction above a threshold, an empirical CDF for quantile mapping, the median and the
+ * inter-quartile range of a field or of an error field (mifc_fexpr_levels makes x - y first) and histogram verification
+ * need the shape of the distribution, and the reference's callers copy the whole batch to the host for it.  Counts and
+ * order statistics do not depend on the order of work: both entries are defined exactly and give the same bits whatever
+ * the launch shape, the memory kind or the staging.
+ * Common inputs: fields[f], up to 8 batches [nlev][ny][nx], with flags fdefined_in[f * nlev + k] (NULL: SOME_DEFINED);
+ * optional mask, a float [ny][nx] shared by all levels and fields, with one flag fdef_mask (the plane a caller passes to
+ * mifc_hstats_levels as weight works here: only whether a cell is defined matters); optional box, a HOST
+ * int[4] = {i0, i1, j0, j1}, half-open (NULL: the whole level); undef, memkind.
+ *   1. Included cell (rule 1 of mifc_hstats_levels without minus).  Cell (j, i) of field f and level k is included iff
+ *      i0 <= i < i1 and j0 <= j < j1; x = fields[f][k][j][i] is defined, is_defined(flag == ALL_DEFINED, x, undef) -- a
+ *      stored undef or a NaN under ALL_DEFINED is a value --; with mask, mask[j][i] is defined by fdef_mask.
+ * mifc_hdist_histogram_levels:
+ *   2. Edges.  edges is a HOST float[nfields * nedges], each field with its own edges[f][0 .. nedges), 1 <= nedges <= 1024,
+ *      strictly ascending under < (so -0.0 and +0.0 cannot both be edges), none a NaN; -inf and +inf are allowed.
+ *   3. Bins.  The bin of an included x that is no NaN is b = #{e : edges[f][e] <= x} with the IEEE comparison: b = 0 below
+ *      the first edge, b = nedges at or above the last, -0.0 and +0.0 in the same bin; numpy.searchsorted(edges, x,
+ *      side="right").  An included NaN is counted in a slot of its own.
+ *   4. Output.  hist is int[nfields][nlev][nrows][nedges + 2], where memkind says: slots 0 .. nedges are the bins, slot
+ *      nedges + 1 is the NaN count; excluded cells are counted nowhere (the caller knows the box).  mode is MIFC_HSTATS_AREA
+ *      (one result per field and level, nrows = 1) or MIFC_HSTATS_ROWS (one per grid row of the box, nrows = j1 - j0, row r
+ *      is grid row j0 + r; the sum over the rows is the AREA result, and on a latitude-longitude grid an exact
+ *      area-weighted histogram is a small weighted sum over rows on the caller's side).  Counts fit an int: nx * ny <=
+ *      2^31 - 1.
+ * mifc_hdist_quantile_levels (AREA only):
+ *   5. n is the number of included cells of (field, level).  Order and rank are rules 3 and 4 of mifc_ensembleQuantiles word
+ *      for word: the included values sorted ascending in IEEE total order, -0 < +0, every NaN above +inf (the result is
+ *      then some NaN); method MIFC_QUANTILE_LOWER, ii = (int)(((float)n * p) / 100.0f) in float, clamped to n - 1, the
+ *      result x[ii] bit for bit; MIFC_QUANTILE_LINEAR, h = ((double)(n - 1) * (double)p) / 100.0, k = (int)h, t = h - k,
+ *      the result x[k] bit for bit where t == 0, else (float)(x[k] + t * (x[k+1] - x[k])) in double, every operation
+ *      rounded, no contraction.  percentiles is a HOST float[nq], 1 <= nq <= 16, each in [0, 100].
+ *   6. Output.  quant is float[nfields][nlev][nq], where memkind says, undef where n == 0; quant[f] is a level batch of
+ *      shape (nlev, 1, nq).  fdefined_q[f * nlev + k] (HOST) is ALL_DEFINED, or NONE_DEFINED where n == 0.  The result is
+ *      defined without reference to any algorithm.
+ *   7. Refusals.  A refused call returns 0, writes nothing and gives the reason in mifc_last_error(): nlev < 1; nfields
+ *      outside 1..8; nx < 1 or ny < 1; nx * ny > 2^31 - 1; a bad memkind; a box that is empty or outside the grid; an unknown
+ *      mode or method; nedges outside 1..1024; nq outside 1..16; a null pointer that is required; an edge that is a NaN or
+ *      not above the edge before it (the field and the index are named); a p that is NaN or outside [0, 100]; an output
+ *      that overlaps an input by byte range; a call made while a mifc_graph capture is open.
+ * (Restated in numpy in tests/hdist_restate.py; the arithmetic of the rules is mi-fieldcalc_amd/csrc/mifc_hdist_rules.h.)
+ * Device memory is used where it is (16-byte loads where every row of every batch is on the 16-byte grid, else dwords),
+ * with one synchronisation at the end.  Host memory works at any size: counts add, so the histogram stages a band of rows
+ * of every level at a time; an order statistic needs all of its level, so the percentiles stage chunks of whole levels,
+ * never less than one; both within MIFC_HDIST_CHUNK_MIB of device memory (default 256), which also bounds the counters of
+ * the selection.  Not offered: weighted (non-integer) histograms; percentiles per row; two-dimensional
+ * (joint) histograms; uniform-bin shortcuts that are not defined by the edge comparisons.
+ * mifc_last_hdist_form: the launch shape of the calling thread's last mifc_hdist_* call, a diagnostic for tests:
+ * "entry=hist|quant mode=area|rows|lower|linear v=4|1 nf=<fields> nbins=<bins of the histogram, digits of a pass> mask=0|1
+ * tested=0|1 prefix=<the fewest key bits that the extremes of a (field, level) share> passes=<the most digit passes a
+ * (field, level) needed> launches=<walks over the cells> bands=<n> chunks=<n>"; "" before the first call. */
+int mifc_hdist_histogram_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                                const float* edges, int nedges, const float* mask, int fdef_mask, const int* box, int mode, int* hist,
+                                float undef, int memkind);
+int mifc_hdist_quantile_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                               const float* percentiles, int nq, int method, const float* mask, int fdef_mask, const int* box,
+                               float* quant, int* fdefined_q, float undef, int memkind);
+const char* mifc_last_hdist_form(void);
 
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the

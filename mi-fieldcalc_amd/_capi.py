@@ -171,6 +171,10 @@ SIGNATURES = {
     # EXTENSION: a register program per cell over level batches (fields, planes, fres: host tables of pointers; the rest host arrays)
     "mifc_fexpr_levels": ("i", ["ctx", "i", "i", "i", "p", "i", "p", "i", "p", "i", "p", "i", "p", "i", "pi", "i", "p", "pi", "f", "i"]),
     "mifc_last_fexpr_form": ("s", []),
+    # EXTENSION: area histograms and exact percentiles of level batches (fields: host table of pointers; edges, percentiles, box: host arrays)
+    "mifc_hdist_histogram_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "i", "pi", "i", "p", "f", "i"]),
+    "mifc_hdist_quantile_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "i", "p", "i", "pi", "p", "pi", "f", "i"]),
+    "mifc_last_hdist_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

@@ -32,6 +32,8 @@ struct Env
   int pvort_chunk_mib = 0;        // MIFC_PVORT_CHUNK_MIB (> 0): device staging of a host-memory mifc_pvort_* call, a band of rows and its neighbour rows at a time (default 256)
   int hinterp_chunk_mib = 0;      // MIFC_HINTERP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hinterp_levels call, whole levels at a time (default 256); mifc_hinterp_vector_levels too
   int hstats_chunk_mib = 0;       // MIFC_HSTATS_CHUNK_MIB (> 0): device staging of a host-memory mifc_hstats_levels call, a band of rows at a time (default 256)
+  int hdist_chunk_mib = 0;        // MIFC_HDIST_CHUNK_MIB (> 0): device staging of a host-memory mifc_hdist_* call (bands of rows, chunks of levels) and the digit counters of the selection, a block of levels at a time (default 256)
+  bool hdist_aggregate = true;    // MIFC_HDIST_AGGREGATE=0: the counters of the mifc_hdist_* kernels take every lane's runs one by one, without the wave's ballot (A/B, tests; the counts are the same)
   int hremap_chunk_mib = 0;       // MIFC_HREMAP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hremap_levels call, whole levels at a time (default 256)
   int fexpr_chunk_mib = 0;        // MIFC_FEXPR_CHUNK_MIB (> 0): device staging of a host-memory mifc_fexpr_levels call, a band of rows at a time (default 256)
   int hremap_level_chunk = 0;     // MIFC_HREMAP_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the hremap kernel takes; A/B, tests)

@@ -60,6 +60,8 @@ void env_reload()
   e.pvort_chunk_mib = positive_int("MIFC_PVORT_CHUNK_MIB");
   e.hinterp_chunk_mib = positive_int("MIFC_HINTERP_CHUNK_MIB");
   e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
+  e.hdist_chunk_mib = positive_int("MIFC_HDIST_CHUNK_MIB");
+  e.hdist_aggregate = not_zero("MIFC_HDIST_AGGREGATE");
   e.hremap_chunk_mib = positive_int("MIFC_HREMAP_CHUNK_MIB");
   e.hremap_level_chunk = positive_int("MIFC_HREMAP_LEVEL_CHUNK");
   e.fexpr_chunk_mib = positive_int("MIFC_FEXPR_CHUNK_MIB");

@@ -775,6 +775,79 @@ struct HstatsCombineParams
 };
 hipError_t launch_hstats_combine(const HstatsCombineParams& prm, hipStream_t stream);
 
+// ------------------------------------ area histograms and exact percentiles of level batches (mifc_hdist.hip), EXTENSION
+// One walk over the included cells of (field, level) -- the rules of mifc_hdist_* (include/mifc.h), their arithmetic in
+// mifc_hdist_rules.h -- serves three purposes (HdistParams::what): HDIST_COUNT bins every cell against the field's edges,
+// HDIST_EXTENT finds n and the smallest and largest key, HDIST_DIGIT counts one digit of the selection.  A workgroup owns
+// rows_per_group rows of the box of one field (grid.z) and walks the levels blockIdx.y, + gridDim.y, ...; its 256 lanes
+// take four consecutive cells each, 1024 columns a trip, one 16-byte load where every row is on the 16-byte grid (vec4)
+// or four dwords.  The planes hold the rows that the caller staged: row r of the launch is row plane_row0 + r of the
+// planes and result row out_row0 + r of a ROWS histogram.  Level k of the launch is level lev0 + k of the call (the
+// level table and the results are indexed by that, the units of the selection by k).
+const int HDIST_COUNT = 0, HDIST_EXTENT = 1, HDIST_DIGIT = 2;
+const int HDIST_GROUP_SLOTS = 4; // prefixes whose digit counters a workgroup keeps in LDS at a time
+// the selection's state of one (field, level), device memory; written by the extent walk, the plan and the scan kernels
+struct HdistUnit
+{
+  unsigned int n, kmin, kmax; // pass 0 (the init kernel: 0, 0xffffffff, 0)
+  int passes, pass_shift[3], pass_width[3];
+  int nranks;               // distinct ranks wanted, ascending
+  unsigned int rank_left[32]; // the rank inside the prefix found so far
+  unsigned int rank_key[32];  // the bits of the key found so far, the others zero
+  int rank_slot[32];          // which of the prefixes below is this rank's
+  int nslots;                 // distinct prefixes of the coming pass, ascending
+  unsigned int slot_prefix[32];
+  int qk[16], qk1[16]; // per percentile: which ranks are x[k] and x[k1]
+  double qt[16];
+};
+struct HdistParams
+{
+  int what;
+  int nx, nlev, lev0, unit_levels; // nlev: levels of this launch, lev0: the call's level of its level 0
+  int nfields;
+  int i0, i1;                          // the box's columns
+  int rows, plane_row0, out_row0;      // the box's rows in the planes
+  int rows_per_group;
+  int tested, mask_all, vec4;
+  int plain;        // the LDS counters without the wave's ballot (A/B: MIFC_HDIST_AGGREGATE=0)
+  int level_blocks; // grid.y (set by launch_hdist_walk)
+  float undef;
+  long stride;
+  const float* fields[8];
+  const float* mask; // null: none
+  const unsigned int* lev_bits;
+  // HDIST_COUNT
+  int nedges, out_rows, per_row;      // per_row: a result per row (ROWS), else one (AREA)
+  const unsigned int* edge_keys;      // [call fields][nedges]
+  int* hist;                          // [nfields][call nlev][out_rows][nedges + 2]
+  int call_nlev;
+  // HDIST_EXTENT, HDIST_DIGIT
+  int pass, slot_stride;
+  HdistUnit* units;         // [nfields][unit_levels]
+  unsigned int* digit_hist; // [unit][slot_stride][HDIST_DIGIT_BINS]
+};
+struct HdistWalkShape
+{
+  int groups, level_blocks; // grid.x, grid.y
+};
+HdistWalkShape hdist_walk_shape(const HdistParams& prm);
+hipError_t launch_hdist_walk(const HdistParams& prm, hipStream_t stream);
+struct HdistSelectParams
+{
+  int nunits, unit_levels, lev0, call_nlev; // units = [nfields][unit_levels]
+  int nq, method, pass, slot_stride;
+  float undef;
+  const float* percentiles; // [nq], device memory
+  HdistUnit* units;
+  const unsigned int* digit_hist;
+  float* quant[8]; // [call nlev][nq] each
+  u64* n_undefined; // [nfields][call nlev]
+};
+hipError_t launch_hdist_init(const HdistSelectParams& prm, hipStream_t stream);  // the units before the extent walk
+hipError_t launch_hdist_plan(const HdistSelectParams& prm, hipStream_t stream);  // behind the extent walk: ranks, digits
+hipError_t launch_hdist_scan(const HdistSelectParams& prm, hipStream_t stream);  // behind the digit walk of `pass`
+hipError_t launch_hdist_final(const HdistSelectParams& prm, hipStream_t stream); // the percentiles, the counters
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
