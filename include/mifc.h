@@ -367,6 +367,21 @@ enum { MIFC_QUANTILE_LOWER = 0, MIFC_QUANTILE_LINEAR = 1 };
 int mifc_ensembleQuantiles(mifc_ctx* ctx, int method, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nmem,
                            const float* percentiles, int nq, float* const* fres, int* fdefined_out, float undef, int memkind);
 
+/* mifc_last_ensemble_form: the launch shape of the calling thread's last successful call of mifc_sumFields, mifc_meanValue,
+ * mifc_stddevValue, mifc_extremeValue, mifc_probability, mifc_ensemble_levels or mifc_ensembleQuantiles, a diagnostic for
+ * tests ("" before the first; a refused call and a call on no cells leave it as it was):
+ *   "entry=single c=4|1 tail=0|1 ..."                         c: cells per lane; tail: the 16-byte launch was followed by
+ *                                                             the scalar launch for the last n % 4 cells
+ *   "entry=levels c=4|1 welford=0|1 flagged=0|1 np=0|3|8 ..."  the template arguments of the kernel instance that ran (a
+ *                                                             list of stddev and one to three probabilities reports
+ *                                                             flagged=1; c=1 is the one scalar instance, 1 1 8)
+ *   "entry=quantiles tier=8|16|32|64|0 ..."                   the sorting network's capacity, 0: the bisection
+ * each followed by "inline=1|0 launches=<n> lev_chunk=<levels> cell_chunk=<cells> partials=0|1": kernel arguments (1) or
+ * device table (0); the kernel launches of the call, one per staged chunk (two for single with tail=1); the staging plan
+ * (for single 1 and nx * ny); whether the undefined counts went through the per-workgroup table.  Where a call staged
+ * several chunks, c, the template arguments and partials are those of its first launch. */
+const char* mifc_last_ensemble_form(void);
+
 /* ---- EXTENSION: interpolation of level batches to constant surfaces ------------------------------------------
  * Not a miutil::fieldcalc function: the reference leaves the step from model levels to the pressure (or height, or
  * isentropic) surfaces its plevel* / ilevel* operators work on to its caller.  nfields fields of [nlev][ny][nx] and one

@@ -185,6 +185,12 @@ class Context(_ReferenceOps, _LevelBatchOps, _BatchedOps):
         tests): mode as a string, the other keys as ints."""
         return _parse_form(self._lib.mifc_last_hstats_form(), ("mode",))
 
+    def last_ensemble_form(self):
+        """The launch shape of this thread's last call of one of the five ensemble reductions, ensembleStatistics or
+        ensembleQuantiles as a dict (mifc_last_ensemble_form; a diagnostic for tests): entry as a string ("single",
+        "levels", "quantiles"), the other keys as ints."""
+        return _parse_form(self._lib.mifc_last_ensemble_form(), ("entry",))
+
     def last_vrotate_form(self):
         """The launch shape of this thread's last vrotate_levels call as a dict of ints (mifc_last_vrotate_form; a diagnostic
         for tests)."""

@@ -162,6 +162,7 @@ SIGNATURES = {
     # EXTENSION: horizontal statistics of level batches (fields, minus, mean: host tables of pointers; pivot, box: host arrays; stats: double)
     "mifc_hstats_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "p", "i", "pi", "i", "i", "p", "p", "pi", "f", "i"]),
     "mifc_last_hstats_form": ("s", []),
+    "mifc_last_ensemble_form": ("s", []),
     # EXTENSION: level batches regridded by a sparse weight table (the plan: rowptr, col, w where memkind says; nnz: long long*)
     "mifc_hremap_plan_create": ("p", ["ctx", "i", "i", "p", "p", "p", "i"]),
     "mifc_hremap_plan_destroy": (None, ["p"]),

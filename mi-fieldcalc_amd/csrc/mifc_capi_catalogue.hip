@@ -3,6 +3,7 @@
 // and its host-evaluated scalars (powf of a level pressure, unit factors), then
 // one launch of the templated pointwise kernel (mifc_pointwise.hip).
 #include "mifc_ctx.h"
+#include "mifc_memberbatch.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -174,6 +175,17 @@ int run_ensemble(mifc_ctx* c, mifc::EnsembleParams P, int nx, int ny, const floa
   if (!st.finish()) // also: `table` and `flags` were read by their copies
     return 0;
   *fdefined_out = mifc_classify(pinned_counts(c)[0], (u64)n);
+  if (n > 0) { // (launch_ensemble launches nothing for no cells)
+    mifc_host::EnsembleForm form;
+    form.entry = mifc_host::EnsembleForm::SINGLE;
+    form.c = mifc::ensemble_vec4(P) ? 4 : 1;
+    form.tail = (form.c == 4 && (n & 3) != 0) ? 1 : 0;
+    form.inline_args = P.n_inline;
+    form.launches = 1 + form.tail;
+    form.lev_chunk = 1;
+    form.cell_chunk = n;
+    mifc_host::note_ensemble_form(form);
+  }
   return 1;
 }
 

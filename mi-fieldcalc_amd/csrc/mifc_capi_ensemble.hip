@@ -143,13 +143,28 @@ int mifc_ensemble_levels(mifc_ctx* c, int nx, int ny, int nlev, const float* con
   const size_t gx = (size_t)mifc::ensemble_levels_blocks(P.n, mifc::ensemble_levels_vec4(P));
   P.partials = partials_for(c, (size_t)1024 * (size_t)mifc::ENSLV_SLOTS * gx * b.lev_chunk, &cap);
   P.partials_cap = P.partials ? cap : 0;
+  EnsembleForm form; // the shape of the first launch: the ragged last range of a level may take the scalar form
   auto launch = [&]() -> int {
     P.vector_ok = b.aligned && (P.nlev == 1 || (P.n & 3) == 0);
+    if (b.launches == 0) {
+      const mifc::EnsLevelsShape s = mifc::ensemble_levels_shape(P);
+      form.c = s.c;
+      form.welford = s.welford ? 1 : 0;
+      form.flagged = s.flagged ? 1 : 0;
+      form.np = s.np;
+      form.partials = s.partials ? 1 : 0;
+    }
     MIFC_LAUNCH(c, mifc::launch_ensemble_levels(P, c->stream));
     return 1;
   };
   if (!b.run(c, a, P, 3 * (size_t)nlev, launch) || !b.finish(c, st)) // (15 counters per level of the context's 5)
     return 0;
+  form.entry = EnsembleForm::LEVELS;
+  form.inline_args = P.inline_args;
+  form.launches = b.launches;
+  form.lev_chunk = b.lev_chunk;
+  form.cell_chunk = b.cell_chunk;
+  note_ensemble_form(form);
   for (int k = 0; k < nproducts; ++k)
     for (int l = 0; l < nlev; ++l)
       products[k].fdefined[l] = b.classify((size_t)slot_of[k] * (size_t)nlev + (size_t)l, cells);

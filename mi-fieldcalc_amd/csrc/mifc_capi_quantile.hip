@@ -89,7 +89,10 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
   int cap = 0;
   P.partials = partials_for(c, (size_t)1024 * (size_t)mifc::quantile_blocks((int)b.cell_chunk) * b.lev_chunk, &cap);
   P.partials_cap = P.partials ? cap : 0;
+  EnsembleForm form;
   auto launch = [&]() -> int {
+    if (b.launches == 0)
+      form.partials = mifc::quantile_partials(P) ? 1 : 0;
     MIFC_LAUNCH(c, mifc::launch_quantiles(P, c->stream));
     return 1;
   };
@@ -99,6 +102,13 @@ int mifc_ensembleQuantiles(mifc_ctx* c, int method, int nx, int ny, int nlev, co
     MIFC_HIP(c, hipMemcpyAsync(fres[q], b.out[(size_t)q], a.bytes(), hipMemcpyDeviceToDevice, c->stream));
   if (!b.finish(c, st)) // (the table was read by its copy)
     return 0;
+  form.entry = EnsembleForm::QUANTILES;
+  form.tier = mifc::quantile_tier(nmem);
+  form.inline_args = P.inline_args;
+  form.launches = b.launches;
+  form.lev_chunk = b.lev_chunk;
+  form.cell_chunk = b.cell_chunk;
+  note_ensemble_form(form);
   for (int l = 0; l < nlev; ++l)
     fdefined_out[l] = nmem == 0 ? MIFC_NONE_DEFINED : b.classify((size_t)l, cells);
   return 1;

@@ -214,7 +214,7 @@ template <int OP>
 hipError_t launch_ens(const EnsembleParams& prm, hipStream_t stream)
 {
   const int block = 256;
-  if (prm.vector_ok && prm.n >= 4) {
+  if (ensemble_vec4(prm)) {
     const int n4 = prm.n >> 2;
     int g = (n4 + block - 1) / block;
     hipLaunchKernelGGL((ensemble_kernel<OP, true>), dim3(g < 1 ? 1 : g), dim3(block), 0, stream, prm);

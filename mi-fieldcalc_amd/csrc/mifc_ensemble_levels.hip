@@ -322,12 +322,13 @@ void launch_tier(const EnsLevelsParams& P, int np, dim3 grid, hipStream_t stream
 {
   if (np == 0)
     launch_shape<4, WELFORD, FLAGGED, 0>(P, grid, stream);
-  else if (np <= 3)
-    // <true, false, 3> is left out: the compiler reserves a 36-byte private segment for it that no instruction touches,
-    // and a dispatch would set scratch up for it; such a list runs on the shape with the flagged family switched off by `live`
-    launch_shape<4, WELFORD, WELFORD || FLAGGED, 3>(P, grid, stream);
-  else
+  else if (np == 8)
     launch_shape<4, WELFORD, FLAGGED, 8>(P, grid, stream);
+  else if constexpr (!WELFORD || FLAGGED)
+    // <true, false, 3> is left out: the compiler reserves a 36-byte private segment for it that no instruction touches,
+    // and a dispatch would set scratch up for it; such a list runs on the shape with the flagged family switched off by
+    // `live` (ensemble_levels_shape says so)
+    launch_shape<4, WELFORD, FLAGGED, 3>(P, grid, stream);
 }
 
 } // namespace
@@ -337,26 +338,24 @@ hipError_t launch_ensemble_levels(const EnsLevelsParams& prm, hipStream_t stream
   if (prm.n <= 0 || prm.nlev <= 0 || (prm.live & ((1u << ENSLV_SLOTS) - 1u)) == 0)
     return hipSuccess;
   EnsLevelsParams P = prm;
-  const bool vec4 = ensemble_levels_vec4(P);
-  const int gx = ensemble_levels_blocks(P.n, vec4);
+  const EnsLevelsShape s = ensemble_levels_shape(P);
+  const int gx = ensemble_levels_blocks(P.n, s.c == 4);
   const int gy = P.nlev < 65535 ? P.nlev : 65535;
   // big levels: per-workgroup counts in partials[slot][level][workgroup], added up behind the launch
-  const bool parts = P.partials && gx >= 2048 && (long)ENSLV_SLOTS * gx * P.nlev <= (long)P.partials_cap;
+  const bool parts = s.partials;
   if (!parts)
     P.partials = nullptr;
   const dim3 grid(gx, gy);
-  const bool welford = (P.live >> 2) & 1u, flagged = (P.live & 0x79u) != 0; // slots 0, 3..6
-  const int np = __builtin_popcount(P.live >> ENSLV_PROB0); // the host fills the probability slots from the first
-  if (!vec4) // the scalar form: one shape with everything in it, the slots switched by `live`
+  if (s.c == 1) // the scalar form: one shape with everything in it, the slots switched by `live`
     launch_shape<1, true, true, ENSLV_NPROB>(P, grid, stream);
-  else if (welford && flagged)
-    launch_tier<true, true>(P, np, grid, stream);
-  else if (welford)
-    launch_tier<true, false>(P, np, grid, stream);
-  else if (flagged)
-    launch_tier<false, true>(P, np, grid, stream);
+  else if (s.welford && s.flagged)
+    launch_tier<true, true>(P, s.np, grid, stream);
+  else if (s.welford)
+    launch_tier<true, false>(P, s.np, grid, stream);
+  else if (s.flagged)
+    launch_tier<false, true>(P, s.np, grid, stream);
   else
-    launch_tier<false, false>(P, np, grid, stream);
+    launch_tier<false, false>(P, s.np, grid, stream);
   hipError_t e = hipGetLastError();
   for (int k = 0; k < ENSLV_SLOTS && e == hipSuccess && parts; ++k)
     if ((P.live >> k) & 1u)

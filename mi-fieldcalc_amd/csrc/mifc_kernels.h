@@ -199,6 +199,11 @@ struct EnsembleParams
   const float* fields_inline[64];
   unsigned char flags_inline[64];
 };
+// the 16-byte launch (four cells per lane), which a scalar launch for the last n % 4 cells follows; else one scalar launch
+inline bool ensemble_vec4(const EnsembleParams& P)
+{
+  return P.vector_ok && P.n >= 4;
+}
 hipError_t launch_ensemble(const EnsembleParams& prm, hipStream_t stream);
 
 // ------------------------------------ percentiles across ensemble members (mifc_quantile.hip), EXTENSION
@@ -244,6 +249,12 @@ inline int quantile_blocks(int n)
 {
   const long want = ((long)n + 255) / 256;
   return (int)(want < 1 ? 1 : (want > 65535 ? 65535 : want));
+}
+// big levels: the counts of a launch go through the partial-count table
+inline bool quantile_partials(const QuantileParams& P)
+{
+  const int gx = quantile_blocks(P.n);
+  return P.partials && gx >= 2048 && (long)gx * P.nlev <= (long)P.partials_cap;
 }
 hipError_t launch_quantiles(const QuantileParams& prm, hipStream_t stream);
 
@@ -297,6 +308,30 @@ inline int ensemble_levels_blocks(int n, bool vec4)
 inline bool ensemble_levels_vec4(const EnsLevelsParams& P)
 {
   return P.vector_ok && P.n >= 4 && (P.n & 3) == 0;
+}
+// The kernel instance a launch takes and whether its counts go through the partial-count table: the launcher dispatches
+// on it and mifc_last_ensemble_form reports it.  c == 1 is the one scalar shape with everything in it; with c == 4 `np` is
+// the room for probability slots (0, 3 or 8), and a list with Welford, one to three probabilities and no flagged product
+// runs on the flagged shape (see launch_ensemble_levels).
+struct EnsLevelsShape
+{
+  int c;
+  bool welford, flagged;
+  int np;
+  bool partials;
+};
+inline EnsLevelsShape ensemble_levels_shape(const EnsLevelsParams& P)
+{
+  EnsLevelsShape s;
+  const bool vec4 = ensemble_levels_vec4(P);
+  const int gx = ensemble_levels_blocks(P.n, vec4);
+  const int np = __builtin_popcount(P.live >> ENSLV_PROB0); // the host fills the probability slots from the first
+  s.c = vec4 ? 4 : 1;
+  s.welford = !vec4 || ((P.live >> 2) & 1u);
+  s.np = !vec4 ? ENSLV_NPROB : np == 0 ? 0 : np <= 3 ? 3 : 8;
+  s.flagged = !vec4 || (P.live & 0x79u) != 0 || (s.welford && s.np == 3); // slots 0, 3..6
+  s.partials = P.partials && gx >= 2048 && (long)ENSLV_SLOTS * gx * P.nlev <= (long)P.partials_cap;
+  return s;
 }
 hipError_t launch_ensemble_levels(const EnsLevelsParams& prm, hipStream_t stream);
 

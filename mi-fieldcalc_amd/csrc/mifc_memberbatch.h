@@ -70,6 +70,7 @@ struct MemberBatch
   std::vector<float*> out;       // (an entry may point one elsewhere before run())
   size_t lev_chunk = 0, cell_chunk = 0;
   bool aligned = true;           // every mem[] and out[] is on the 16-byte grid
+  int launches = 0;              // of run(): one per staged chunk
   int build(mifc_ctx* c, const MemberBatchCall& a, bool with_none, float* const* out_host, int nout, size_t n_counts);
   // device memory: one chunk of everything; host memory: two scratch blocks of `budget` bytes at most, the arrays a
   // multiple of 64 floats apart; cells_by_4: a range of cells that is not a level's last is a multiple of 4
@@ -97,6 +98,7 @@ struct MemberBatch
         P.stride = (long)nc;
         if (!launch())
           return 0;
+        launches += 1;
         for (size_t k = 0; host && k < out.size(); ++k)
           MIFC_HIP(c, hipMemcpyAsync(out_host_[k] + off, out[k], bytes, hipMemcpyDeviceToHost, c->stream));
       }
@@ -109,6 +111,20 @@ private:
   std::vector<u64> counts_;
   float* const* out_host_ = nullptr;
 };
+
+// mifc_last_ensemble_form (include/mifc.h): what the calling thread's last member-batch call launched.  An entry fills
+// one in as it decides and notes it once, when the call has succeeded; it is formatted only when asked for.
+struct EnsembleForm
+{
+  enum { NONE = -1, SINGLE, LEVELS, QUANTILES };
+  int entry = NONE;
+  int c = 0, tail = 0;                  // SINGLE, LEVELS
+  int welford = 0, flagged = 0, np = 0; // LEVELS: the template arguments of the instance
+  int tier = 0;                         // QUANTILES
+  int inline_args = 0, launches = 0, partials = 0;
+  size_t lev_chunk = 0, cell_chunk = 0;
+};
+void note_ensemble_form(const EnsembleForm& form);
 
 // What does not fit the kernel arguments: sections (where from, bytes), each on the 16-byte grid of one device block that
 // is uploaded once from `host`, which has to live until the stream is synchronised.  dev[i]: where section i is.

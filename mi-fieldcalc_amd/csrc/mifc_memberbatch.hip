@@ -2,9 +2,20 @@
 #include "mifc_memberbatch.h"
 
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 
 namespace mifc_host {
+
+namespace {
+thread_local EnsembleForm t_form;
+thread_local char t_form_text[192];
+} // namespace
+
+void note_ensemble_form(const EnsembleForm& form)
+{
+  t_form = form;
+}
 
 int refuse(mifc_ctx* c, const MemberBatchCall& a, const std::string& why)
 {
@@ -116,3 +127,23 @@ int upload_table(mifc_ctx* c, Staging& st, std::vector<unsigned char>& host, std
 }
 
 } // namespace mifc_host
+
+extern "C" const char* mifc_last_ensemble_form(void)
+{
+  using mifc_host::EnsembleForm;
+  const EnsembleForm& f = mifc_host::t_form;
+  char* const text = mifc_host::t_form_text;
+  const size_t room = sizeof mifc_host::t_form_text;
+  int at = 0;
+  if (f.entry == EnsembleForm::NONE)
+    return "";
+  if (f.entry == EnsembleForm::SINGLE)
+    at = std::snprintf(text, room, "entry=single c=%d tail=%d", f.c, f.tail);
+  else if (f.entry == EnsembleForm::LEVELS)
+    at = std::snprintf(text, room, "entry=levels c=%d welford=%d flagged=%d np=%d", f.c, f.welford, f.flagged, f.np);
+  else
+    at = std::snprintf(text, room, "entry=quantiles tier=%d", f.tier);
+  std::snprintf(text + at, room - (size_t)at, " inline=%d launches=%d lev_chunk=%zu cell_chunk=%zu partials=%d", f.inline_args, f.launches,
+                f.lev_chunk, f.cell_chunk, f.partials);
+  return text;
+}

@@ -273,7 +273,7 @@ hipError_t launch_quantiles(const QuantileParams& prm, hipStream_t stream)
   const int gy = prm.nlev < 65535 ? prm.nlev : 65535;
   QuantileParams P = prm;
   // big levels: per-workgroup counts in partials[level][workgroup], added up behind the launch
-  const bool parts = P.partials && gx >= 2048 && (long)gx * P.nlev <= (long)P.partials_cap;
+  const bool parts = quantile_partials(P);
   if (!parts)
     P.partials = nullptr;
   const dim3 grid(gx, gy), block(256);

@@ -82,3 +82,34 @@ def test_chunk_budget_is_read_with_the_rest_of_the_environment():
     assert '"MIFC_ENSEMBLE_CHUNK_MIB"' in env
     host = open(os.path.join(ROOT, "mi-fieldcalc_amd", "csrc", "mifc_capi_ensemble.hip")).read()
     assert "ensemble_chunk_mib" in host and "getenv" not in host
+
+
+def test_launch_shape_read_back_is_declared_exported_and_bound():
+    text = open(os.path.join(ROOT, "include", "mifc.h")).read()
+    code = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    assert re.search(r"\bconst\s+char\s*\*\s*mifc_last_ensemble_form\s*\(\s*void\s*\)\s*;", code), "include/mifc.h does not declare it"
+    doc = re.search(r"/\*\s*mifc_last_ensemble_form:.*?\*/", text, flags=re.S)
+    assert doc, "include/mifc.h does not document it"
+    for key in ("entry=single", "entry=levels", "entry=quantiles", "c=", "tail=", "welford=", "flagged=", "np=", "tier=", "inline=", "launches=",
+                "lev_chunk=", "cell_chunk=", "partials="):
+        assert key in doc.group(0), key
+    lib = ctypes.CDLL(LIB)
+    assert hasattr(lib, "mifc_last_ensemble_form"), "libmifc.so does not export mifc_last_ensemble_form"
+    import mi_fieldcalc_amd as fc
+    import mi_fieldcalc_amd._capi as capi
+
+    assert capi.SIGNATURES["mifc_last_ensemble_form"] == ("s", [])
+    assert callable(fc.Context.last_ensemble_form)
+    # "" before the first call of a thread: read on a fresh one (no GPU is touched)
+    import threading
+
+    lib.mifc_last_ensemble_form.restype = ctypes.c_char_p
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(lib.mifc_last_ensemble_form()))
+    t.start()
+    t.join()
+    assert seen == [b""]
+    # every entry notes its shape through the one function of the member-batch driver
+    csrc = os.path.join(ROOT, "mi-fieldcalc_amd", "csrc")
+    for name in ("mifc_capi_catalogue.hip", "mifc_capi_ensemble.hip", "mifc_capi_quantile.hip"):
+        assert "note_ensemble_form(" in open(os.path.join(csrc, name)).read(), name
