@@ -1106,6 +1106,78 @@ int mifc_hdist_quantile_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const fl
                                float* quant, int* fdefined_q, float undef, int memkind);
 const char* mifc_last_hdist_form(void);
 
+/* ---- EXTENSION: trajectories through a series of wind level batches --------------------------------------------
+ * Not a miutil::fieldcalc function: the reference's callers carry points along the wind of a level on the host, slice by
+ * slice -- where the air of a plume came from, a backward trajectory from every grid cell (an origin map), temperature or
+ * humidity along the path.  Every other entry takes the state at one time; this one moves along the time axis.  nt time
+ * slices of the wind components u, v ([nlev][ny][nx] each), their times, the map-ratio planes of the stencil operators
+ * and npos start positions go in.  Every level carries its own copy of the npos particles: particle (k, p) moves with the
+ * wind of level k only.  The index speed of a wind component u is u * xmapr per second (compare 0.5 * xmapr *
+ * (f[i+1] - f[i-1]) in the stencil operators), of v it is v * ymapr.  The run goes from slice j_start to slice j_end,
+ * forward (j_end > j_start, dir = +1) or backward (dir = -1); nslots = |j_end - j_start| + 1, slot n belongs to slice
+ * j_start + n * dir.  xres, yres and tres[f] are [nslots][nlev][npos].
+ * Definition.  Every operation is an IEEE double operation rounded on its own, with no contraction; results are bit for
+ * bit this definition.  Per particle (k, p):
+ *   1. Start.  x = xpos0[p], y = ypos0[p].  Usable is exactly rule 1 of mifc_hinterp_levels: defined, and inside
+ *      [0, nx - 1] x [0, ny - 1] in double.  An unusable start makes the particle lost from slot 0 on.  Otherwise slot 0
+ *      holds xpos0[p], ypos0[p] bit for bit, and the state is (xd, yd) = ((double)x, (double)y).
+ *   2. Sampling a plane at a double position (xd, yd).  First the inside test of rule 1:
+ *      xd >= 0.0 && xd <= nx - 1 && yd >= 0.0 && yd <= ny - 1; a NaN fails it.  Then rule 2 of mifc_hinterp_levels gives
+ *      i0, j0, a, b; column i0 + 1 is needed only when a != 0, row j0 + 1 only when b != 0.  Rule 3 gives the definedness
+ *      of each needed corner under the flag of that plane.  Rule 5 gives the value, without its final rounding to float:
+ *      r0 when b == 0, else r0 + b * (r1 - r0).
+ *   3. Index velocity G(xd, yd, w) in the interval from slice A to slice B = A + dir.  If the inside test fails, the
+ *      particle is lost.  Sample u_A, u_B, v_A, v_B of level k, and xmapr, ymapr, by 2; the planes use flag fdef_map.  Both
+ *      slices are needed at every w: if any needed corner of any of the six planes is undefined, the particle is lost.
+ *      uu = w == 0 ? u_A : (w == 1 ? u_B : u_A + w * (u_B - u_A)), and vv likewise.  G = (uu * mx, vv * my).
+ *   4. Interval.  tau = times[B] - times[A] (negative on a backward run), h = tau / (double)nsub, hh = 0.5 * h,
+ *      w_s = (double)s / (double)nsub.  For s = 0 .. nsub - 1: g0 = G(x_s, w_s); x* = x_s + h * g0 (each component); then
+ *      niter times: g1 = G(x*, w_{s+1}), then x* = x_s + hh * (g0 + g1) (Petterssen); niter = 0 is the Euler step;
+ *      x_{s+1} = x*.  After the last substep the position must pass the inside test, otherwise the particle is lost.
+ *   5. Slot.  A particle that survives the interval to slice B writes (float)xd, (float)yd to slot n + 1, and its state
+ *      becomes those floats widened again.  Because the state passes through float at every slice, a run j0 -> j2 equals
+ *      the run j0 -> j1 followed by a run j1 -> j2 started from slot 1's positions, bit for bit; this also makes the
+ *      result independent of how the call is staged.
+ *   6. Lost.  A particle lost in the interval n -> n + 1 has undef in xres, yres and every tres[f] at slots n + 1 ..;
+ *      its earlier slots stay.
+ *   7. Trace.  At every slot where the particle is alive, tres[f] is exactly rules 2-5 of mifc_hinterp_levels, BILINEAR
+ *      with a float result, taken from slice j_start + n * dir of trace field f, level k, at the slot's float position.  A
+ *      trace hole gives undef at that slot only; the particle is not lost.  By definition it equals a
+ *      mifc_hinterp_levels call on that level with nlev = 1, at the positions of that slot.
+ *   8. Flags.  g = 0: checkDefined(lost particles at slot n, level k; npos); g = 1 + f: checkDefined(lost + trace holes;
+ *      npos).  A computed value is never counted.
+ * (Restated in Python in tests/htraj_restate.py; the arithmetic is mi-fieldcalc_amd/csrc/mifc_htraj_rules.h.)
+ * Arguments.  `u`, `v`: HOST arrays of nt pointers, one per time slice, each to a [nlev][ny][nx] batch where memkind
+ * says.  `fdefined_in`: HOST int[2 * nt * nlev], index (c * nt + t) * nlev + k with c = 0 for u and c = 1 for v; NULL means
+ * all SOME_DEFINED.  `times`: HOST double[nt], in seconds.  `xmapr`, `ymapr`: [ny][nx] planes in the memory kind of the
+ * fields, flag fdef_map.  `xpos0`, `ypos0`: float[npos], in grid-index units as in mifc_hinterp_levels, in the memory kind
+ * of the fields.  `trace`: HOST array of ntrace * nt pointers, index f * nt + t, each to [nlev][ny][nx]; `fdef_trace`: HOST
+ * int[ntrace * nt * nlev], index (f * nt + t) * nlev + k, NULL means all SOME_DEFINED.  Only slices between j_start and
+ * j_end inclusive are dereferenced.  `tres`: HOST array of ntrace pointers.  `fdefined_out`: HOST
+ * int[(1 + ntrace) * nslots * nlev], index (g * nslots + n) * nlev + k; g = 0 is the positions (x and y share it),
+ * g = 1 + f is trace field f.  Any alignment of any pointer is accepted.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nt < 2, nlev < 1 or
+ * npos < 1; nx < 1 or ny < 1; nx or ny above 2^24 (the bounds must be exact floats, so that rounding a double inside the
+ * grid cannot leave it); nx * ny > 2^31 - 1; j_start or j_end outside 0..nt-1, or j_start == j_end; nsub outside 1..64;
+ * niter outside 0..8; ntrace outside 0..4; a times[j] in the used range that is not finite, or used times that are not
+ * strictly increasing with j; undef >= 0 && undef <= max(nx, ny) - 1 (a computed position could then not be told from a
+ * hole; a NaN undef is fine); a required null pointer (trace, tres and fdef_trace may be null when ntrace == 0); an
+ * output that overlaps an input or another output by byte range; a bad memkind; a call made while a mifc_graph capture
+ * is open.
+ * Device memory is used where it is: one launch per interval, queued interval after interval, one synchronisation at
+ * the end.  Host memory works at any size, because levels are independent: the call stages a chunk of levels and walks
+ * the intervals with two slice buffers (slice B goes up while A stays); the map planes and the start positions go up
+ * once, the slots come down.  MIFC_HTRAJ_CHUNK_MIB of device memory (default 256), but never less than one level
+ * (DESIGN.md 4.26).
+ * mifc_last_htraj_form: the launch shape of the calling thread's last mifc_htraj_levels call, a diagnostic for tests:
+ * "niter=<n> nsub=<n> ntrace=<n> tested=0|1 blocks=<grid.x> level_chunks=<grid.y> chunk=<levels per chunk>
+ * intervals=<n> launches=<n> staged=<level chunks staged from host, 0 for device memory>"; "" before the first call. */
+int mifc_htraj_levels(mifc_ctx* ctx, int nx, int ny, int nlev, int nt, const float* const* u, const float* const* v, const int* fdefined_in,
+                      const double* times, const float* xmapr, const float* ymapr, int fdef_map, int npos, const float* xpos0,
+                      const float* ypos0, int j_start, int j_end, int nsub, int niter, const float* const* trace, const int* fdef_trace,
+                      int ntrace, float* xres, float* yres, float* const* tres, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_htraj_form(void);
+
 /* ---- neighbourhood statistics ----------------------------------------------
  * neighbourProbFunctions .h:297 / .cc:2862; neighbourFunctions .h:300 / .cc:2955.  Bit-identical to the
  * reference, its quirks included: the input flag must be ALL_DEFINED; the constants are truncated to int

@@ -176,6 +176,10 @@ SIGNATURES = {
     "mifc_hdist_histogram_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "i", "pi", "i", "p", "f", "i"]),
     "mifc_hdist_quantile_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "i", "p", "i", "pi", "p", "pi", "f", "i"]),
     "mifc_last_hdist_form": ("s", []),
+    # EXTENSION: trajectories through a series of wind level batches (u, v, trace, tres: host tables of pointers; times: host double array)
+    "mifc_htraj_levels": ("i", ["ctx", "i", "i", "i", "i", "p", "p", "pi", "p", "p", "p", "i", "i", "p", "p", "i", "i", "i", "i", "p", "pi", "i",
+                                "p", "p", "p", "pi", "f", "i"]),
+    "mifc_last_htraj_form": ("s", []),
     # the ensemble reductions over a level batch (fields: host table of pointers; products: host array of EnsProduct)
     "mifc_ensemble_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "f", "i"]),
     # neighbourhood statistics (constants: host float array)

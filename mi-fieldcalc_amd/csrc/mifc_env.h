@@ -34,6 +34,8 @@ struct Env
   int hstats_chunk_mib = 0;       // MIFC_HSTATS_CHUNK_MIB (> 0): device staging of a host-memory mifc_hstats_levels call, a band of rows at a time (default 256)
   int hdist_chunk_mib = 0;        // MIFC_HDIST_CHUNK_MIB (> 0): device staging of a host-memory mifc_hdist_* call (bands of rows, chunks of levels) and the digit counters of the selection, a block of levels at a time (default 256)
   bool hdist_aggregate = true;    // MIFC_HDIST_AGGREGATE=0: the counters of the mifc_hdist_* kernels take every lane's runs one by one, without the wave's ballot (A/B, tests; the counts are the same)
+  int htraj_chunk_mib = 0;        // MIFC_HTRAJ_CHUNK_MIB (> 0): device staging of a host-memory mifc_htraj_levels call, a chunk of whole levels with two slice buffers and every slot (default 256)
+  int htraj_level_chunk = 0;      // MIFC_HTRAJ_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the htraj kernel walks; A/B, tests)
   int hremap_chunk_mib = 0;       // MIFC_HREMAP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hremap_levels call, whole levels at a time (default 256)
   int fexpr_chunk_mib = 0;        // MIFC_FEXPR_CHUNK_MIB (> 0): device staging of a host-memory mifc_fexpr_levels call, a band of rows at a time (default 256)
   int hremap_level_chunk = 0;     // MIFC_HREMAP_LEVEL_CHUNK (> 0 overrides the levels a workgroup of the hremap kernel takes; A/B, tests)

@@ -62,6 +62,8 @@ void env_reload()
   e.hstats_chunk_mib = positive_int("MIFC_HSTATS_CHUNK_MIB");
   e.hdist_chunk_mib = positive_int("MIFC_HDIST_CHUNK_MIB");
   e.hdist_aggregate = not_zero("MIFC_HDIST_AGGREGATE");
+  e.htraj_chunk_mib = positive_int("MIFC_HTRAJ_CHUNK_MIB");
+  e.htraj_level_chunk = positive_int("MIFC_HTRAJ_LEVEL_CHUNK");
   e.hremap_chunk_mib = positive_int("MIFC_HREMAP_CHUNK_MIB");
   e.hremap_level_chunk = positive_int("MIFC_HREMAP_LEVEL_CHUNK");
   e.fexpr_chunk_mib = positive_int("MIFC_FEXPR_CHUNK_MIB");

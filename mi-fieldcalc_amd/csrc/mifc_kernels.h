@@ -883,6 +883,42 @@ hipError_t launch_hdist_plan(const HdistSelectParams& prm, hipStream_t stream); 
 hipError_t launch_hdist_scan(const HdistSelectParams& prm, hipStream_t stream);  // behind the digit walk of `pass`
 hipError_t launch_hdist_final(const HdistSelectParams& prm, hipStream_t stream); // the percentiles, the counters
 
+// ------------------------------------ trajectories through a series of wind level batches (mifc_htraj.hip), EXTENSION
+// One launch carries the particles of `nlev` levels through ONE interval, from slice A to slice B, by the rules of
+// mifc_htraj_levels (include/mifc.h), their arithmetic in mifc_htraj_rules.h: an iterated gather.  A lane owns particle p
+// of one level for all nsub * (1 + niter) evaluations, a workgroup 256 consecutive particles and the levels
+// [blockIdx.y * chunk, + chunk) of the launch, one after the other.  Every pointer is the caller's for level 0 of the
+// launch and the slot the interval starts from: level k of a plane lies at its pointer + k * in_stride (the map planes
+// are [ny][nx]); a slot is [levels][npos], level k at + k * npos: the one the interval starts from at x, y, t[f], the
+// one it ends in slot_stride further.  The interval starts from the positions that the launch before left at x, y -- an
+// undef there is a lost particle --, the launch with `first` set from xpos0, ypos0, shared by all levels, and it writes
+// the slot it starts from too (the starts bit for bit, the trace of slice A).  bits[k] is the HTRAJ_*_BIT word
+// of level k in this interval (read only by the tested instances).  The counters, zeroed by the caller, are rows of
+// call_nlev, one per (g, slot): counts[(g * nslots + e) * call_nlev + k], e = 0 the starting slot and 1 the ending one;
+// g = 0 the lost particles, g = 1 + f the trace holes of field f under live particles.  Every access is a single dword:
+// any alignment.
+struct HtrajParams
+{
+  int nx, ny, npos;
+  int nlev;      // levels of this launch
+  int call_nlev; // levels of the call: the row length of the counters
+  int chunk;     // levels per workgroup: grid.y = ceil(nlev / chunk) (set by launch_htraj from htraj_level_chunk)
+  int nslots;
+  int nsub, niter, ntrace;
+  int tested; // 0: every plane of the call is ALL_DEFINED, no value is tested
+  int first;
+  float undef;
+  double tau; // times[B] - times[A]
+  long in_stride, slot_stride;
+  const float *uA, *uB, *vA, *vB, *xmapr, *ymapr;
+  const float* trace[8]; // [0 .. 3] of slice A (read by the first launch only), [4 .. 7] of slice B
+  const float *xpos0, *ypos0; // the start positions [npos] (read by the first launch only)
+  float *x, *y, *t[4];
+  const unsigned int* bits;
+  u64* counts;
+};
+hipError_t launch_htraj(const HtrajParams& prm, hipStream_t stream);
+
 // -------------------------------------------------------------------- stencils
 enum StencilOp {
   ST_RELVORT = 0,    // :1843
