@@ -426,6 +426,67 @@ int mifc_vinterp_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* co
                         const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, const float* targets,
                         int ntargets, int method, float* const* fres, int* fdefined_out, float undef, int memkind);
 
+/* ---- EXTENSION: interpolation of level batches to per-cell target surfaces -----------------------------------
+ * Not a miutil::fieldcalc function.  mifc_vinterp_* above takes a level batch to surfaces that are one number for the
+ * whole grid; here the target is a plane: the hybrid levels of another model or orography (a2 + b2 * ps2), a
+ * terrain-following height set, the LCL pressure of mifc_vparcel_*, the COORD_OF_MAX of mifc_vlayer_*, ps - 30 hPa.
+ * nfields fields of [nlev][ny][nx], one coordinate per level and cell and ntargets target planes go in, nfields fields
+ * of [ntargets][ny][nx] come out.  For each cell i and target t:
+ *   1. Source coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it (mifc_vregrid_hlevels: the float product,
+ *      then the float sum, defined where ps[i] is; mifc_vregrid_fields: coord[k][i], defined under fdef_coord[k]).
+ *      mifc_vregrid_levels: c_k = levels[k] for every cell, always defined.
+ *   2. Target.  ct = tcoord[t][i] is usable when is_defined(fdef_tcoord[t] == ALL_DEFINED, ct, undef) holds and ct is
+ *      not NaN; with MIFC_VINTERP_LOG it must also be > 0.  Otherwise every field is undef at (t, i): a result, not a
+ *      refusal.
+ *   3. Bracket.  Of the k, 0 <= k < nlev - 1, with c_k and c_{k+1} both defined and
+ *      min(c_k, c_{k+1}) <= ct <= max(c_k, c_{k+1}), MIFC_VREGRID_FROM_FIRST = 0 takes the smallest and
+ *      MIFC_VREGRID_FROM_LAST = 1 the largest.  The comparisons are float comparisons (-0 == +0; a NaN coordinate never
+ *      brackets).  No monotonicity and no level order is assumed.
+ *   4. Values, weight, result.  Rules 3 to 6 of mifc_vinterp_* word for word, on the pair (k, k + 1) in that
+ *      orientation whichever way the levels are searched: x_k and x_{k+1} defined under their flags, else undef;
+ *      MIFC_VINTERP_LOG with min(c_k, c_{k+1}) <= 0 at the bracket: undef; c_k == c_{k+1}: x_k bit for bit; otherwise
+ *      w in double from ct, c_k, c_{k+1} (MIFC_VINTERP_LOG: from the log() of each, all three taken in double per
+ *      cell) and (float)((double)x_k + w * ((double)x_{k+1} - (double)x_k)).
+ *   5. No bracket.  MIFC_VREGRID_OUTSIDE_UNDEF = 0: undef.  MIFC_VREGRID_OUTSIDE_CLAMP = 1: over the levels of the cell
+ *      whose coordinate is defined and not NaN, kmin is the lowest index that attains the smallest coordinate and kmax
+ *      the lowest index that attains the largest.  ct < c_kmin gives x_kmin, ct > c_kmax gives x_kmax, each copied bit
+ *      for bit without arithmetic (also with MIFC_VINTERP_LOG), undef where that value is undefined under its level's
+ *      flag.  Anything else -- a ct inside the range that holes left without a bracket, a cell without a usable level
+ *      -- is undef.
+ *   6. Flags.  fdefined_out[f * ntargets + t] = checkDefined(cells that rules 2 to 5 left undef, nx * ny).  A computed
+ *      NaN or infinity is a value: not counted.
+ * MIFC_VINTERP_LINEAR is bit for bit this definition (restated in numpy in tests/vregrid_restate.py).
+ * MIFC_VINTERP_LOG depends on the device's double log(): a result is the definition's float or its neighbour, undef
+ * cells and flags are exact -- the statement mifc_vinterp_* makes.
+ * Arguments: `fields`, `fdefined_in`, `ps`, `alevel`, `blevel`, `coord`, `fdef_coord`, `fres` as for mifc_vinterp_*,
+ * nfields 1..8; `levels` a HOST float[nlev]; `tcoord` is [ntargets][ny][nx] in the memory kind of the fields,
+ * `fdef_tcoord` a HOST int[ntargets], NULL = all SOME_DEFINED; ntargets 1..256; `method` MIFC_VINTERP_LINEAR or
+ * MIFC_VINTERP_LOG; `fdefined_out` a HOST int[nfields * ntargets], field-major.
+ * Refused calls return 0, write nothing and give the reason in mifc_last_error().  They are: nlev < 2; nfields outside
+ * 1..8; ntargets outside 1..256; a negative nx or ny; a null pointer (fdefined_in, fdef_coord and fdef_tcoord may be
+ * null); an unknown method, from or outside; a NaN in levels; hybrid form only: a level that the reference's bad_hlevel
+ * (FieldCalculations.cc:298) rejects; an output that overlaps an input, the coordinate, ps, tcoord or another output; a
+ * call made while a mifc_graph capture is open.  nx * ny == 0: the flags are ALL_DEFINED, nothing else is written.
+ * memkind works as everywhere else; host memory works at any size: the call stages a band of rows at a time, tcoord as
+ * one more group of ntargets planes, within MIFC_VREGRID_CHUNK_MIB of device memory (default 256).  Every input level is
+ * read once per pass of `tb` target planes.  mifc_last_vregrid_form: a diagnostic for tests, the
+ * calling thread's last call that launched: "v=4|1 tb=<planes per pass> passes=<n> from=first|last outside=undef|clamp
+ * coord=hybrid|field|levels method=linear|log launches=<n>". */
+enum { MIFC_VREGRID_FROM_FIRST = 0, MIFC_VREGRID_FROM_LAST = 1 };
+enum { MIFC_VREGRID_OUTSIDE_UNDEF = 0, MIFC_VREGRID_OUTSIDE_CLAMP = 1 };
+int mifc_vregrid_hlevels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                         const float* ps, int fdef_ps, const float* alevel, const float* blevel, const float* tcoord,
+                         const int* fdef_tcoord /* HOST int[ntargets], NULL = SOME_DEFINED */, int ntargets, int method, int from,
+                         int outside, float* const* fres, int* fdefined_out, float undef, int memkind);
+int mifc_vregrid_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* coord, const int* fdef_coord /* HOST int[nlev], NULL = SOME_DEFINED */, const float* tcoord,
+                        const int* fdef_tcoord, int ntargets, int method, int from, int outside, float* const* fres,
+                        int* fdefined_out, float undef, int memkind);
+int mifc_vregrid_levels(mifc_ctx* ctx, int nx, int ny, int nlev, const float* const* fields, const int* fdefined_in, int nfields,
+                        const float* levels /* HOST float[nlev] */, const float* tcoord, const int* fdef_tcoord, int ntargets,
+                        int method, int from, int outside, float* const* fres, int* fdefined_out, float undef, int memkind);
+const char* mifc_last_vregrid_form(void);
+
 /* ---- EXTENSION: layer integrals, means and extremes of level batches -----------------------------------------
  * Not a miutil::fieldcalc function: the reference leaves every reduction over levels (precipitable water, a layer-mean
  * wind, the maximum wind of a layer and where it sits, a pressure-weighted mean between two surfaces) to a host loop of

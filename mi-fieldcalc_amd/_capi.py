@@ -139,6 +139,10 @@ SIGNATURES = {
     "mifc_vcumul_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
     "mifc_vcumul_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "i", "p", "i", "p", "pi", "p", "p", "pi", "f", "i"]),
     "mifc_last_vcumul_form": ("s", []),
+    "mifc_vregrid_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "i", "p", "p", "p", "pi", "i", "i", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_vregrid_fields": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "pi", "p", "pi", "i", "i", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_vregrid_levels": ("i", ["ctx", "i", "i", "i", "p", "pi", "i", "p", "p", "pi", "i", "i", "i", "i", "p", "pi", "f", "i"]),
+    "mifc_last_vregrid_form": ("s", []),
     # EXTENSION: parcel ascent over level batches (t: the batch itself; the six outputs: any may be None; fdefined_out: host int[5 + nlev])
     "mifc_vparcel_hlevels": ("i", ["ctx", "i", "i", "i", "p", "pi", "p", "i", "p", "p", "i", "i", "p", "i", "p", "i", "p", "i",
                                    "p", "p", "p", "p", "p", "p", "pi", "f", "i"]),

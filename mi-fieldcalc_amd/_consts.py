@@ -15,6 +15,10 @@ VDERIV_METHODS = {"centred": 0, "weighted": 1}
 # the methods and walk directions of mifc_vcumul_* (MIFC_VCUMUL_*)
 VCUMUL_METHODS = {"linear": 0, "log": 1}
 VCUMUL_FROM = {"first": 0, "last": 1}
+# the search directions and the treatment of targets outside the column of mifc_vregrid_* (MIFC_VREGRID_*)
+VREGRID_METHODS = {"linear": 0, "log": 1}  # MIFC_VINTERP_LINEAR / _LOG
+VREGRID_FROM = {"first": 0, "last": 1}
+VREGRID_OUTSIDE = {"undef": 0, "clamp": 1}
 # the walk directions of mifc_vparcel_* (MIFC_VPARCEL_FROM_*) and the order of its outputs in the flags
 VPARCEL_FROM = {"first": 0, "last": 1}
 VPARCEL_OUTPUTS = ("cape", "cin", "plcl", "plfc", "pel", "tparcel")

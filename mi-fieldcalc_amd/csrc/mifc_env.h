@@ -28,6 +28,9 @@ struct Env
   int vlayer_chunk_mib = 0;       // MIFC_VLAYER_CHUNK_MIB (> 0): device staging of a host-memory mifc_vlayer_* call, a band of rows at a time (default 256)
   int vderiv_chunk_mib = 0;       // MIFC_VDERIV_CHUNK_MIB (> 0): device staging of a host-memory mifc_vderiv_* call, a band of rows at a time (default 256); mifc_vrotate_levels too
   int vcumul_chunk_mib = 0;       // MIFC_VCUMUL_CHUNK_MIB (> 0): device staging of a host-memory mifc_vcumul_* call, a band of rows at a time (default 256)
+  int vregrid_chunk_mib = 0;      // MIFC_VREGRID_CHUNK_MIB (> 0): device staging of a host-memory mifc_vregrid_* call, a band of rows at a time (default 256)
+  int vregrid_tb = 0;             // MIFC_VREGRID_TB (> 0): target planes per pass of the mifc_vregrid_* kernel, capped at what the form allows (A/B, tools/bench_vregrid.py; the results are the same)
+  int vregrid_v = 0;              // MIFC_VREGRID_V=4: the mifc_vregrid_* kernel takes four cells per lane where the batch is on the 16-byte grid (default: one cell per lane everywhere, the faster form; A/B, tools/bench_vregrid.py, tests; the results are the same)
   int vparcel_chunk_mib = 0;      // MIFC_VPARCEL_CHUNK_MIB (> 0): device staging of a host-memory mifc_vparcel_* call, a band of rows at a time (default 256)
   int pvort_chunk_mib = 0;        // MIFC_PVORT_CHUNK_MIB (> 0): device staging of a host-memory mifc_pvort_* call, a band of rows and its neighbour rows at a time (default 256)
   int hinterp_chunk_mib = 0;      // MIFC_HINTERP_CHUNK_MIB (> 0): device staging of a host-memory mifc_hinterp_levels call, whole levels at a time (default 256); mifc_hinterp_vector_levels too

@@ -56,6 +56,9 @@ void env_reload()
   e.vlayer_chunk_mib = positive_int("MIFC_VLAYER_CHUNK_MIB");
   e.vderiv_chunk_mib = positive_int("MIFC_VDERIV_CHUNK_MIB");
   e.vcumul_chunk_mib = positive_int("MIFC_VCUMUL_CHUNK_MIB");
+  e.vregrid_chunk_mib = positive_int("MIFC_VREGRID_CHUNK_MIB");
+  e.vregrid_tb = positive_int("MIFC_VREGRID_TB");
+  e.vregrid_v = positive_int("MIFC_VREGRID_V");
   e.vparcel_chunk_mib = positive_int("MIFC_VPARCEL_CHUNK_MIB");
   e.pvort_chunk_mib = positive_int("MIFC_PVORT_CHUNK_MIB");
   e.hinterp_chunk_mib = positive_int("MIFC_HINTERP_CHUNK_MIB");

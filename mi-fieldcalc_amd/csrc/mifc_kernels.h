@@ -376,6 +376,43 @@ __host__ __device__ inline int vinterp_key(int bits)
 }
 hipError_t launch_vinterp(const VinterpParams& prm, hipStream_t stream);
 
+// ------------------------------------ level batches to per-cell target surfaces (mifc_vregrid.hip), EXTENSION
+// One launch walks the `nlev` levels of `n` columns once, in index order (from = 0) or against it (from = 1), and serves
+// the `nt` target planes tcoord + (t0 + t) * in_stride of one pass, nt <= tb <= VREGRID_MAX_TB; the host launches again
+// for the targets beyond.  A lane keeps the targets of its own cells in LDS (nt * 256 * V floats of dynamic LDS, with nt = tb at most
+// VREGRID_MAX_LDS bytes, which with the counting table stays within 64 KiB: tb * V <= 63).  Fields, outputs, `coord`, `ab`, `lev_bits`, the counters and vec4 as in
+// VinterpParams; hybrid with no_ps: nothing is read per cell, ps counts as 0 (the `levels` form: ab = levels[nlev] then
+// nlev zeros).  Bit t of tc_all: target plane t0 + t is flagged ALL_DEFINED.
+const int VREGRID_MAX_FIELDS = 8, VREGRID_MAX_TARGETS = 256, VREGRID_MAX_TB = 32, VREGRID_TB = 24, VREGRID_MAX_LDS = 65536 - 1024;
+struct VregridParams
+{
+  int hybrid;  // coordinate kind: 1 = alevel + blevel * ps, 0 = field
+  int no_ps;   // hybrid only: 1 = the `levels` form
+  int method;  // MIFC_VINTERP_LINEAR / MIFC_VINTERP_LOG
+  int from;    // MIFC_VREGRID_FROM_FIRST / _FROM_LAST
+  int outside; // MIFC_VREGRID_OUTSIDE_UNDEF / _OUTSIDE_CLAMP
+  int nfields; // 1 .. VREGRID_MAX_FIELDS
+  int n;       // columns of this launch
+  int nlev;    // >= 2
+  int tb;      // targets a pass has room for
+  int nt;      // targets of this pass, 1 .. tb
+  int t0;      // the call's target of the pass' target 0 (target planes, outputs, counters)
+  int nt_call; // targets of the whole call: the distance between the counters of two fields
+  int ps_all;  // hybrid: ps is flagged ALL_DEFINED
+  int vec4;
+  unsigned int tc_all;
+  float undef;
+  long in_stride, out_stride;
+  const float* fields[VREGRID_MAX_FIELDS];
+  float* out[VREGRID_MAX_FIELDS];
+  const float* coord;
+  const float* tcoord;
+  const float* ab;
+  const unsigned int* lev_bits;
+  u64* n_undefined; // [nfields][nt_call], zeroed by the caller
+};
+hipError_t launch_vregrid(const VregridParams& prm, hipStream_t stream);
+
 // ------------------------------------ layer integrals, means and extremes of level batches (mifc_vlayer.hip), EXTENSION
 // One launch walks the `nlev` levels of `n` columns once for up to VLAYER_PASS fields and stores, per field, the products
 // whose `slot` is not negative: product code p (MIFC_VLAYER_*, 1..6) goes to out[f] + slot[p - 1] * out_stride.  The host

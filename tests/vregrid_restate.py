@@ -1,0 +1,156 @@
+"""Numpy restatement of mifc_vregrid_hlevels / mifc_vregrid_fields / mifc_vregrid_levels (include/mifc.h, "interpolation of
+level batches to per-cell target surfaces"), written from the numbered rules there: the oracle of tests/test_vregrid_cpu.py
+and tests/test_gpu_vregrid.py.  The coordinate in float32, the weight and the result step by step in float64 (every ufunc
+rounds once, so nothing is contracted).  Every cell goes through the rules on its own; the cells of a plane are merely
+carried side by side in arrays.  Generators and constants come from vinterp_restate, the arithmetic does not.
+
+MISTAKES names departures from the definition that a kernel could plausibly make; regrid(..., mistakes=(...)) makes
+them, and tests/test_vregrid_cpu.py holds that each one changes the bits of the cases aimed at it."""
+import numpy as np
+
+from vinterp_restate import ALL_DEFINED, LINEAR, LOG, NONE_DEFINED, SOME_DEFINED, UNDEF, classify, hybrid_coordinate, is_defined  # noqa: F401
+
+FROM_FIRST, FROM_LAST = 0, 1
+OUTSIDE_UNDEF, OUTSIDE_CLAMP = 0, 1
+
+MISTAKES = ("last bracket under from first", "pair oriented by the walk", "clamp to the end levels", "clamp inside a gap", "highest index on a tie",
+            "weight from a float log", "open bracket end", "undefined target as a number")
+
+
+def regrid(fields, coord, coord_defined, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF, flags=None, fdef_tcoord=None, undef=UNDEF,
+           mistakes=(), log=np.log):
+    """fields float32 (nf, nlev, ny, nx); coord float32 (nlev, ny, nx) and coord_defined bool of the same shape (rule 1);
+    tcoord float32 (nt, ny, nx); flags None (SOME_DEFINED) or (nf, nlev); fdef_tcoord None or (nt,).  Returns (out (nf, nt,
+    ny, nx), flags_out int32 (nf, nt)).  log: the double logarithm of rule 4 (a test moves its results by an ulp).
+    mistakes: names from MISTAKES, not part of the definition."""
+    assert all(m in MISTAKES for m in mistakes), mistakes
+    x = np.asarray(fields, np.float32)
+    nf, nlev, ny, nx = x.shape
+    cells = ny * nx
+    x = x.reshape(nf, nlev, cells)
+    c = np.asarray(coord, np.float32).reshape(nlev, cells)
+    cdef = np.asarray(coord_defined, bool).reshape(nlev, cells)
+    undef = np.float32(undef)
+    tc = np.asarray(tcoord, np.float32)
+    nt = tc.shape[0]
+    tc = tc.reshape(nt, cells)
+    fl = np.full((nf, nlev), SOME_DEFINED) if flags is None else np.asarray(flags).reshape(nf, nlev)
+    ft = [SOME_DEFINED] * nt if fdef_tcoord is None else list(np.asarray(fdef_tcoord).reshape(nt))
+    xdef = np.stack([np.stack([is_defined(fl[f, k] == ALL_DEFINED, x[f, k], undef) for k in range(nlev)]) for f in range(nf)])
+    every = np.arange(cells)
+    out = np.full((nf, nt, cells), undef, np.float32)
+    bad = np.ones((nf, nt, cells), bool)
+    with np.errstate(all="ignore"):
+        # rule 5: the extremes of the usable levels of every cell, the lowest index that attains each
+        usable_c = cdef & ~np.isnan(c)
+        any_level = usable_c.any(axis=0)
+        cmin = np.where(usable_c, c, np.float32(np.inf)).min(axis=0)
+        cmax = np.where(usable_c, c, np.float32(-np.inf)).max(axis=0)
+        at_min, at_max = usable_c & (c == cmin), usable_c & (c == cmax)
+        if "highest index on a tie" in mistakes:
+            kmin, kmax = nlev - 1 - at_min[::-1].argmax(axis=0), nlev - 1 - at_max[::-1].argmax(axis=0)
+        else:
+            kmin, kmax = at_min.argmax(axis=0), at_max.argmax(axis=0)
+        if "clamp to the end levels" in mistakes:
+            top_first = c[0] <= c[nlev - 1]
+            kmin, kmax = np.where(top_first, 0, nlev - 1), np.where(top_first, nlev - 1, 0)
+        for t in range(nt):
+            ct = tc[t]
+            # rule 2
+            if "undefined target as a number" in mistakes:
+                usable = ~np.isnan(ct)
+            else:
+                usable = is_defined(ft[t] == ALL_DEFINED, ct, undef) & ~np.isnan(ct)
+            if method == LOG:
+                usable &= ct > 0
+            # rule 3: the pairs in the order in which the first bracket found is the one to take
+            descending = from_ == FROM_LAST or "last bracket under from first" in mistakes
+            found = np.zeros(cells, bool)
+            for k in (range(nlev - 2, -1, -1) if descending else range(nlev - 1)):
+                lo, hi = np.minimum(c[k], c[k + 1]), np.maximum(c[k], c[k + 1])  # a NaN comes through and fails both comparisons
+                lower = (lo < ct) if "open bracket end" in mistakes else (lo <= ct)
+                br = usable & cdef[k] & cdef[k + 1] & lower & (ct <= hi) & ~found
+                if not br.any():
+                    continue
+                found |= br
+                # rule 4: the pair is (k, k + 1) whichever way it was found
+                a, b = (k + 1, k) if (from_ == FROM_LAST and "pair oriented by the walk" in mistakes) else (k, k + 1)
+                ca, cb = c[a], c[b]
+                da, db, dt = ca.astype(np.float64), cb.astype(np.float64), ct.astype(np.float64)
+                if method == LOG:
+                    if "weight from a float log" in mistakes:
+                        la, lb, lt = (np.log(v).astype(np.float64) for v in (ca, cb, ct))
+                    else:
+                        la, lb, lt = log(da), log(db), log(dt)
+                    w = (lt - la) / (lb - la)
+                    positive = lo > 0
+                else:
+                    w = (dt - da) / (db - da)
+                    positive = np.ones(cells, bool)
+                for f in range(nf):
+                    xa, xb = x[f, a], x[f, b]
+                    ok = xdef[f, a] & xdef[f, b] & positive
+                    xd = xa.astype(np.float64)
+                    v = (xd + w * (xb.astype(np.float64) - xd)).astype(np.float32)
+                    r = np.where(ok, np.where(ca == cb, xa, v), undef)
+                    out[f, t, br] = r[br]
+                    bad[f, t, br] = ~ok[br]
+            # rule 5
+            if outside == OUTSIDE_CLAMP:
+                rest = usable & ~found & any_level
+                below, above = rest & (ct < cmin), rest & (ct > cmax)
+                if "clamp inside a gap" in mistakes:
+                    above |= rest & ~below
+                for pick, k_of in ((below, kmin), (above, kmax)):
+                    for f in range(nf):
+                        value, ok = x[f, k_of, every], xdef[f, k_of, every]
+                        out[f, t, pick] = np.where(ok, value, undef)[pick]  # copied, no arithmetic
+                        bad[f, t, pick] = ~ok[pick]
+    fd = np.array([[classify(int(bad[f, t].sum()), cells) for t in range(nt)] for f in range(nf)], np.int32)
+    return out.reshape(nf, nt, ny, nx), fd
+
+
+def hlevels(fields, ps, alevel, blevel, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF, flags=None, fdef_ps=SOME_DEFINED, fdef_tcoord=None,
+            undef=UNDEF, **kw):
+    c = hybrid_coordinate(ps, alevel, blevel)
+    psd = is_defined(fdef_ps == ALL_DEFINED, np.asarray(ps, np.float32), undef)
+    return regrid(fields, c, np.broadcast_to(psd, c.shape), tcoord, method, from_, outside, flags, fdef_tcoord, undef, **kw)
+
+
+def coord_fields(fields, coord, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF, flags=None, fdef_coord=None, fdef_tcoord=None, undef=UNDEF, **kw):
+    c = np.asarray(coord, np.float32)
+    fc = [SOME_DEFINED] * c.shape[0] if fdef_coord is None else list(fdef_coord)
+    cdef = np.stack([is_defined(fc[k] == ALL_DEFINED, c[k], undef) for k in range(c.shape[0])])
+    return regrid(fields, c, cdef, tcoord, method, from_, outside, flags, fdef_tcoord, undef, **kw)
+
+
+def levels(fields, levs, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF, flags=None, fdef_tcoord=None, undef=UNDEF, **kw):
+    lv = np.asarray(levs, np.float32).ravel()
+    shape = np.shape(fields)[1:]
+    c = np.broadcast_to(lv[:, None, None], shape).astype(np.float32)
+    return regrid(fields, c, np.ones(shape, bool), tcoord, method, from_, outside, flags, fdef_tcoord, undef, **kw)
+
+
+def hybrid_targets(ps_dst, alevel_dst, blevel_dst, undef=UNDEF):
+    """The target batch of hybrid_to_hybrid: a + b * ps_dst like p_hlevel, undef where ps_dst is undef or NaN."""
+    p = np.asarray(ps_dst, np.float32)
+    t = hybrid_coordinate(p, alevel_dst, blevel_dst)
+    t[:, (p == np.float32(undef)) | np.isnan(p)] = np.float32(undef)
+    return t
+
+
+# ---------------------------------------------------------------------------------------------- case generators
+def target_planes(coord, nt, seed, spread=0.15, frac=0.03, undef=UNDEF):
+    """nt target planes around the levels of `coord` (nlev, ny, nx), undefined where it is: plane t follows level
+    t * (nlev - 1) / max(nt - 1, 1) times a factor in 1 -+ spread, so some targets lie beyond both ends of the column; 3 % of them undef."""
+    rng = np.random.default_rng(seed)
+    c = np.asarray(coord, np.float32)
+    nlev = c.shape[0]
+    planes = []
+    for t in range(nt):
+        k = int(round(t * (nlev - 1) / max(nt - 1, 1)))
+        base = np.where(c[k] == np.float32(undef), np.float32(500), c[k])
+        planes.append((base * rng.uniform(1 - spread, 1 + spread, base.shape)).astype(np.float32))
+    tc = np.stack(planes)
+    tc[rng.random(tc.shape) < frac] = undef
+    return tc
