@@ -434,7 +434,8 @@ int mifc_vinterp_fields(mifc_ctx* ctx, int nx, int ny, int nlev, const float* co
  * of [ntargets][ny][nx] come out.  For each cell i and target t:
  *   1. Source coordinate.  c_k exactly as rule 1 of mifc_vinterp_* gives it (mifc_vregrid_hlevels: the float product,
  *      then the float sum, defined where ps[i] is; mifc_vregrid_fields: coord[k][i], defined under fdef_coord[k]).
- *      mifc_vregrid_levels: c_k = levels[k] for every cell, always defined.
+ *      mifc_vregrid_levels: c_k = levels[k] for every cell, always defined, bit for bit (a level of -0 stays -0: its
+ *      sign reaches the result through the weight of rule 4).
  *   2. Target.  ct = tcoord[t][i] is usable when is_defined(fdef_tcoord[t] == ALL_DEFINED, ct, undef) holds and ct is
  *      not NaN; with MIFC_VINTERP_LOG it must also be > 0.  Otherwise every field is undef at (t, i): a result, not a
  *      refusal.

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void vregrid_kernel(const VregridParams P)
     if (P.no_ps) {
 #pragma unroll
       for (int c = 0; c < V; ++c)
-        ps[c] = 0.f; // the `levels` form: a = levels[k], b = 0
+        ps[c] = -0.f; // the `levels` form: a = levels[k], b = +0; 0 * -0 = -0 and a + -0 is a bit for bit, a level of -0 too (a + +0 made it +0)
     } else {
       walk_load<V>(ps, P.coord + at);
       walk_usable_ps<V>(ps, P.ps_all != 0, undef);

@@ -1,19 +1,20 @@
-"""Seeded cases that put the five column-walk families (mifc_vinterp_*, mifc_vlayer_*, mifc_vderiv_*, mifc_vcumul_*,
-mifc_pvort_*) at the ends of the float range (numpy only: no GPU, nothing read from the reference).
+"""Seeded cases that put the six column-walk families (mifc_vinterp_*, mifc_vlayer_*, mifc_vderiv_*, mifc_vcumul_*,
+mifc_pvort_*, mifc_vregrid_*) at the ends of the float range (numpy only: no GPU, nothing read from the reference).
 tests/test_column_range_cpu.py asserts on the CPU that the cases reach what they are meant to reach and that they tell a
 flush to zero, a float intermediate and a key/float mismatch of the vinterp bracket from the definition;
 tests/test_gpu_column_range.py runs them through the library.
 
 A case is a dict:
   label    "<family>-<class>-<kind>-<method>[-<extra>][-nan-undef]-<nx>x<ny>x<nlev>": names the seam
-  family   vinterp | vlayer | vderiv | vcumul | pvort          kind    hybrid | field | levels
+  family   vinterp | vlayer | vderiv | vcumul | pvort | vregrid  kind    hybrid | field | levels
   method   the family's method (vlayer: None)                   klass   huge | tiny | mid
   undef    1e35, or NaN in the "-nan-undef" variant
   fields   float32 (nf, nlev, ny, nx); pvort: u, v, th          flags   int32 (nf, nlev): ALL_DEFINED and SOME_DEFINED mixed
   hybrid:  ps (ny, nx), ab = (alevel, blevel), fdef_c one flag  field:  coord (nlev, ny, nx), fdef_c int32[nlev]
   levels:  levs float32[nlev]
   extras   vinterp: targets | vlayer: lo, hi (numbers or (ny, nx) fields) | vcumul: from_, start, fdef_start, base, fdef_base,
-           scale | pvort: xmapr, ymapr, fcoriolis, scale
+           scale | pvort: xmapr, ymapr, fcoriolis, scale | vregrid: tcoord (nt, ny, nx), fdef_t int32[nt], method, from_, outside
+           (what the call is run with; the case's own `method` names the rule its coordinate was drawn by)
 
 What the ingredients are for:
   fields   per magnitude class a decade chosen so that the RESULT straddles the end of the range: `huge` differences
@@ -37,6 +38,19 @@ The rates and decades are tuned until the conditions asserted in tests/test_colu
 degrade into comparing NaN with NaN or undef with undef.
 
 vinterp_seam_cases() are cases of another kind, for the wave pre-filter of vinterp_kernel: see the section below.
+
+vregrid re-uses vinterp's ingredients unchanged (make_fields, the coordinate and ps specials, the LOG coordinate rule; its
+`levels` kind takes LEVELS_LINEAR_B and LEVELS_LOG) and adds per-cell targets: see "vregrid: the targets" below.  One set of
+arrays (a "base") is run with every (method, from, outside): each combination is a case of its own that shares the
+base's arrays.  A base drawn by the LOG rule is run with both methods.  A base drawn by the LINEAR rule is run with LINEAR, and
+with LOG where at most half of the outputs are holes (log_runs_on_a_linear_base): its coordinates cross zero, MIFC_VINTERP_LOG
+turns away every target <= 0 and every bracket with an end <= 0, and so the `levels` bases (LEVELS_LINEAR_B has one pair
+above zero), the two-level base and the `field` bases under OUTSIDE_UNDEF come to 58 .. 99 % holes -- they would compare
+undef with undef -- while the hybrid bases (17 .. 33 %) and the `field` bases under OUTSIDE_CLAMP (43 .. 50 %) run.
+tests/test_column_range_cpu.py asserts both sides of that line, and that a double log() one ulp off moves nothing on the
+LOG runs of the LINEAR bases either (between neighbours one float apart a target can only be an end: weight 0 or 1 under
+any log()).  vregrid_seam_cases() and
+vregrid_hand_columns() are for the wave interval of vregrid_kernel and for its clamp rule.
 """
 import functools
 import zlib
@@ -48,13 +62,14 @@ import vcumul_restate as vc
 import vderiv_restate as vd
 import vinterp_restate as vi
 import vlayer_restate as vl
+import vregrid_restate as vg
 
 ALL_DEFINED, NONE_DEFINED, SOME_DEFINED = vi.ALL_DEFINED, vi.NONE_DEFINED, vi.SOME_DEFINED
 UNDEF = vi.UNDEF
-FAMILIES = ("vinterp", "vlayer", "vderiv", "vcumul", "pvort")
+FAMILIES = ("vinterp", "vlayer", "vderiv", "vcumul", "pvort", "vregrid")
 CLASSES = ("huge", "tiny", "mid")
 NY, NX_VEC, NX_ODD, NLEV = 9, 68, 67, 7  # 612 cells: four per lane, three waves | 603: one per lane, a partial last wave
-MIN_NLEV = {"vinterp": 2, "vlayer": 2, "vderiv": 2, "vcumul": 2, "pvort": 2}
+MIN_NLEV = {"vinterp": 2, "vlayer": 2, "vderiv": 2, "vcumul": 2, "pvort": 2, "vregrid": 2}
 
 _F = np.float32
 FLT_MAX, FLT_MIN, DENORM_MIN = np.finfo(np.float32).max, np.finfo(np.float32).tiny, _F(2.0) ** _F(-149)
@@ -89,6 +104,7 @@ HUGE_DECADES = {
     ("vderiv", "centred"): (36.8, 38.5), ("vderiv", "weighted"): (36.8, 38.5),
     ("vcumul", "linear"): (36.3, 38.3), ("vcumul", "log"): (35.3, 37.2), ("vcumul", "log-hybrid"): (36.0, 38.0),
     ("pvort", "centred"): (36.8, 38.5), ("pvort", "weighted"): (36.8, 38.5),
+    ("vregrid", "linear"): (36.5, 38.5), ("vregrid", "log"): (36.5, 38.5),  # vinterp's
 }
 TINY_DECADES = (-44.5, -37.6)
 
@@ -254,6 +270,8 @@ def _spec(family, klass):
     """(kind, method, nx, nlev, nan_undef, extra) of the cases of a family and class: every kind and method, both widths,
     one "-nan-undef" variant; the family's minimum nlev once, in the mid class."""
     V, O = NX_VEC, NX_ODD
+    if family == "vregrid":
+        return _vregrid_spec(klass)
     if family == "vinterp":
         s = [("hybrid", "linear", V, NLEV, False, None), ("field", "linear", O, NLEV, False, None), ("field", "log", V, NLEV, False, None),
              ("hybrid", "log", O, NLEV, False, None), ("field", "linear", V, NLEV, True, None)]
@@ -289,6 +307,8 @@ def all_cases():
 
 
 def make_case(family, klass, kind, method, nx, nlev, nan_undef, extra):
+    if family == "vregrid":
+        return make_vregrid_case(klass, kind, method, nx, nlev, nan_undef, extra)
     ny = NY
     parts = [family, klass, kind] + ([method] if method else []) + ([extra] if extra else []) + (["nan-undef"] if nan_undef else [])
     label = "-".join(parts) + "-%dx%dx%d" % (nx, ny, nlev)
@@ -372,6 +392,8 @@ def make_case(family, klass, kind, method, nx, nlev, nan_undef, extra):
             ex["start"], ex["fdef_start"] = start, int(rng.choice([ALL_DEFINED, SOME_DEFINED]))
             ex["base"], ex["fdef_base"] = [base[0], None], [ALL_DEFINED, SOME_DEFINED]
             ex["scale"] = [1.0, 0.5] if log else [1.0, -0.5]
+    elif family == "vregrid":
+        raise AssertionError("vregrid cases are made by make_vregrid_case")
     elif family == "pvort":
         xm = rng.uniform(0.5e-2, 2e-2, (ny, nx)).astype(np.float32)
         ym = rng.uniform(0.5e-2, 2e-2, (ny, nx)).astype(np.float32)
@@ -449,14 +471,290 @@ def vinterp_seam_cases():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ vregrid: the targets
+# Per cell and target plane one of five kinds (`tkind` of a case holds which):
+#   0 on a level    the coordinate of a level of the cell's own column, bit for bit (weight 0 or 1, c_k == c_k+1 next to it)
+#   1 midpoint      of two neighbouring levels, computed in double and rounded
+#   2 beyond        below the smallest or above the largest usable coordinate of the column (for OUTSIDE_CLAMP); where that
+#                   extreme is infinite the other side, where both are a midpoint
+#   3 ordinary      a number drawn like vinterp's targets
+#   4 special       +-0, +-2^-149, +-FLT_MAX, +-inf, NaN, 1e35 and both its neighbours; LOG bases: also -1.5
+# fdef_t is ALL_DEFINED and SOME_DEFINED mixed; a stored 1e35 lies in planes of both.
+TARGET_KINDS = ("on a level", "midpoint", "beyond", "ordinary", "special")
+TARGET_SHARES = (0.25, 0.30, 0.20, 0.20, 0.05)
+TARGET_SPECIALS = np.array([0.0, -0.0, DENORM_MIN, -DENORM_MIN, FLT_MAX, -FLT_MAX, np.inf, -np.inf, np.nan, UNDEF, UNDEF_BELOW, UNDEF_ABOVE], np.float32)
+TARGET_SPECIALS_LOG = np.concatenate([TARGET_SPECIALS, np.array([-1.5], np.float32)])
+VREGRID_COMBOS = [(m, f, o) for m in ("linear", "log") for f in ("first", "last") for o in ("undef", "clamp")]
+# planes per pass of vregrid_kernel: 15 at four cells per lane, 24 at one (mifc_capi_vregrid.hip, pass_targets); a base
+# with one plane more takes two passes in that layout, so the found-mask and the slots in LDS are used again
+VREGRID_NT, VREGRID_TB = 10, {4: 15, 1: 24}
+
+
+def make_targets(rng, c, usable, nt, log, kind, undef):
+    """(tcoord (nt, ny, nx), fdef_t, tkind) for the coordinate c (nlev, ny, nx) with its rule-1 mask."""
+    nlev, ny, nx = c.shape
+    cells = ny * nx
+    cf = c.reshape(nlev, cells)
+    uf = usable.reshape(nlev, cells) & ~np.isnan(cf)
+    every = np.arange(cells)[None]
+    what = rng.choice(len(TARGET_KINDS), size=(nt, cells), p=TARGET_SHARES)
+    with np.errstate(all="ignore"):
+        on_level = cf[rng.integers(0, nlev, (nt, cells)), every]
+        k = rng.integers(0, nlev - 1, (nt, cells))
+        mid = ((cf[k, every].astype(np.float64) + cf[k + 1, every].astype(np.float64)) * 0.5).astype(np.float32)
+        cmin, cmax = np.where(uf, cf, INF).min(axis=0), np.where(uf, cf, -INF).max(axis=0)
+        u = rng.uniform(0.5, 3, (nt, cells)).astype(np.float32)
+        if log:
+            below, above = np.nextafter(cmin * _F(0.5) + 0 * u, _F(0)), np.nextafter(cmax * _F(2) + 0 * u, INF)
+        else:
+            below, above = np.nextafter(cmin - u, -INF), np.nextafter(cmax + u, INF)
+        can_below, can_above = np.isfinite(cmin) & ((cmin > 0) | (not log)), np.isfinite(cmax)
+        side = rng.random((nt, cells)) < 0.5
+        take_below = can_below[None] & (side | ~can_above[None])
+        beyond = np.where(take_below, below, np.where(can_above[None], above, mid)).astype(np.float32)
+        if log:
+            ordinary = np.exp(rng.uniform(-90, 80, (nt, cells))) if kind != "hybrid" else rng.uniform(0.05, 8, (nt, cells))
+        else:
+            lo, hi = (-0.3, 0.3) if nlev == 2 else (0.05, 7) if kind == "hybrid" else (-2, 6)
+            ordinary = rng.uniform(lo, hi, (nt, cells))
+        special = rng.choice(TARGET_SPECIALS_LOG if log else TARGET_SPECIALS, size=(nt, cells))
+    t = np.choose(what, [on_level, mid, beyond, ordinary.astype(np.float32), special]).astype(np.float32)
+    fdef_t = rng.choice([ALL_DEFINED, SOME_DEFINED], size=nt).astype(np.int32)
+    fdef_t[0], fdef_t[nt - 1] = SOME_DEFINED, ALL_DEFINED
+    for p in (0, nt - 1):  # a stored 1e35 under both flag values
+        at = rng.choice(cells, size=6, replace=False)
+        t[p, at], what[p, at] = UNDEF, 4
+    for p in range(nt):
+        if fdef_t[p] == SOME_DEFINED:
+            at = _sprinkle(t[p], rng, 0.01, np.array([undef], np.float32))
+            what[p, at] = 4
+    return t.reshape(nt, ny, nx), fdef_t, what.astype(np.int8).reshape(nt, ny, nx)
+
+
+def log_runs_on_a_linear_base(kind, nlev, outside):
+    """LOG on a base drawn by the LINEAR rule: where at most half of the outputs are holes (see the module docstring)."""
+    return kind == "hybrid" or (kind == "field" and nlev == NLEV and outside == "clamp")
+
+
+def _vregrid_spec(klass):
+    V, O = NX_VEC, NX_ODD
+    bases = [("hybrid", "linear", V, NLEV, False, VREGRID_TB[4] + 1, ""), ("field", "linear", O, NLEV, False, VREGRID_TB[1] + 1, ""),
+             ("levels", "linear", O, NLEV, False, VREGRID_NT, ""), ("field", "log", V, NLEV, False, VREGRID_NT, ""), ("hybrid", "log", O, NLEV, False, VREGRID_NT, ""),
+             ("levels", "log", V, NLEV, False, VREGRID_NT, ""), ("field", "linear", V, NLEV, True, VREGRID_NT, "")]
+    if klass == "mid":
+        bases += [("field", "linear", O, MIN_NLEV["vregrid"], False, VREGRID_NT, ""), ("hybrid", "linear", V, NLEV, False, VREGRID_NT, "-overflow")]
+    return [(kind, rule, nx, nlev, nan_undef, "t%d.%s.%s.%s%s" % (nt, m, f, o, tail))
+            for kind, rule, nx, nlev, nan_undef, nt, tail in bases for m, f, o in VREGRID_COMBOS
+            if rule == "log" or m == "linear" or log_runs_on_a_linear_base(kind, nlev, o)]
+
+
+@functools.lru_cache(maxsize=None)
+def vregrid_base(klass, kind, rule, nx, nlev, nan_undef, nt, overflow):
+    """The arrays that the combinations of one base share: fields, flags and the coordinate drawn exactly as make_case draws
+    vinterp's, and the targets."""
+    ny = NY
+    label = "-".join(["vregrid", klass, kind, rule, "t%d" % nt] + (["overflow"] if overflow else []) + (["nan-undef"] if nan_undef else [])) + "-%dx%dx%d" % (nx, ny, nlev)
+    rng = np.random.default_rng(_seed(label))
+    undef = _F(np.nan) if nan_undef else UNDEF
+    log = rule == "log"
+    flags = make_flags(rng, 2, nlev)
+    base = dict(family="vregrid", kind=kind, method=rule, klass=klass, undef=undef, flags=flags, base=label)
+    base["fields"] = make_fields(rng, klass, HUGE_DECADES["vregrid", rule], 2, nlev, ny, nx, flags, undef, positive=log)
+    if kind == "hybrid":
+        base["fdef_c"] = int(rng.choice([ALL_DEFINED, SOME_DEFINED]))
+        base["ps"], base["ab"] = make_hybrid(rng, nlev, ny, nx, base["fdef_c"], undef, log, overflow)
+    elif kind == "field":
+        base["fdef_c"] = make_coord_flags(rng, nlev)
+        base["coord"] = (make_coord_log if log else make_coord_linear)(rng, nlev, ny, nx, base["fdef_c"], undef)
+    else:
+        base["levs"] = np.ascontiguousarray(LEVELS_LOG if log else LEVELS_LINEAR_B)
+    c, usable = coordinate_of(base)
+    if log:
+        assert_log_spacing(c, usable)
+    tcoord, fdef_t, tkind = make_targets(rng, c, usable, nt, log, kind, undef)
+    base.update(tcoord=tcoord, fdef_t=fdef_t, tkind=tkind)
+    for v in list(base.values()) + list(base.get("ab", ())):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return base
+
+
+def make_vregrid_case(klass, kind, rule, nx, nlev, nan_undef, extra):
+    overflow = extra.endswith("-overflow")
+    nt, method, from_, outside = extra.replace("-overflow", "").split(".")
+    base = vregrid_base(klass, kind, rule, nx, nlev, nan_undef, int(nt[1:]), overflow)
+    label = "-".join(["vregrid", klass, kind, rule] + extra.split("-") + (["nan-undef"] if nan_undef else [])) + "-%dx%dx%d" % (nx, NY, nlev)
+    case = {k: v for k, v in base.items() if k not in ("tcoord", "fdef_t")}
+    case.update(label=label, extras=dict(tcoord=base["tcoord"], fdef_t=base["fdef_t"], method=method, from_=from_, outside=outside))
+    return case
+
+
+def vregrid_plain(case):
+    """The case in the form of tests/vregrid_cases.py (what tests/test_vregrid_cpu.py hands to the rules header)."""
+    kind, ex = case["kind"], case["extras"]
+    out = dict(kind=kind, fields=case["fields"], tcoord=ex["tcoord"], flags=case["flags"], fdef_t=ex["fdef_t"], undef=case["undef"],
+               coord=case["ps"] if kind == "hybrid" else case["coord"] if kind == "field" else case["levs"])
+    if kind == "hybrid":
+        out.update(ab=case["ab"], fdef_c=case["fdef_c"])
+    elif kind == "field":
+        out["fdef_c"] = case["fdef_c"]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ vregrid: the wave's interval
+# vregrid_kernel skips a pair of levels where the interval [lo, hi] that the pair spans over the WAVE does not meet the
+# interval [tmin, tmax] of the wave's usable targets of the pass: !(lo <= tmax && hi >= tmin), both reduced with fminf /
+# fmaxf from [+inf, -inf].  The skip and the cell's own bracket test can part only where an end of the pair is itself the
+# target and the wave's extreme on that side -- which per-cell random targets never make.  These cases give whole waves
+# (blocks of 256 cells: one wave of four cells per lane, four waves of one) the same column of five levels
+#   X, Ta, <hole>, Tb, Y        X <= Ta <= Tb <= Y
+# and the targets Ta, Tb (and Ta again, with unusable targets sprinkled in): Ta is the smallest target of the wave and the
+# upper end of the only pair that brackets it, Tb the largest and the lower end of its only pair.  The ends run through
+# +-inf, +-FLT_MAX, +-FLT_MIN, +-2^-149 and zero, a zero level against the target of the other sign in both orders.
+# Neighbouring blocks are far apart in value.  Three more blocks: targets that are all unusable; a lane whose coordinates are
+# all NaN (stored, level 0 under an ALL_DEFINED flag) and one whose levels are undefined; one cell whose pairs are (-inf, +inf) (LOG: (2^-149, +inf)).
+_Z = (_F(0.0), _F(-0.0))  # (level, target)
+_ZR = (_F(-0.0), _F(0.0))
+SEAM_ENDS = [(-INF, -FLT_MAX), (-FLT_MAX, -FLT_MIN), (-FLT_MIN, -DENORM_MIN), (-DENORM_MIN, _Z), (-DENORM_MIN, _ZR), (_Z, DENORM_MIN), (_ZR, DENORM_MIN),
+             (DENORM_MIN, FLT_MIN), (FLT_MIN, FLT_MAX), (FLT_MAX, INF), (INF, INF), (-INF, -INF)]
+SEAM_ENDS_LOG = [(_D2, FLT_MIN), (FLT_MIN, FLT_MAX), (FLT_MAX, INF), (INF, INF), (None, DENORM_MIN)]  # None: no pair below (LOG needs X > 0)
+SEAM_EXTRA_BLOCKS = ("unusable targets", "a lane without levels", "a pair from -inf to +inf")
+VREGRID_SEAM_NLEV, VREGRID_SEAM_NT = 5, 3
+
+
+def _interleaved(n):
+    half = (n + 1) // 2
+    return [j // 2 + (half if j % 2 else 0) for j in range(n) if j // 2 + (half if j % 2 else 0) < n]
+
+
+@functools.lru_cache(maxsize=None)
+def vregrid_seam_bases():
+    out = []
+    for rule, ends in (("linear", SEAM_ENDS), ("log", SEAM_ENDS_LOG)):
+        log = rule == "log"
+        order = [ends[j] for j in _interleaved(len(ends))]
+        nb = len(order) + len(SEAM_EXTRA_BLOCKS)
+        nlev, nt, ny, nx = VREGRID_SEAM_NLEV, VREGRID_SEAM_NT, nb, SEAM_BLOCK
+        label = "vregrid-seam-field-%s-%dx%dx%d" % (rule, nx, ny, nlev)
+        rng = np.random.default_rng(_seed(label))
+        flags = make_flags(rng, 2, nlev)
+        fields = make_fields(rng, "mid", None, 2, nlev, ny, nx, flags, UNDEF, positive=log)
+        c = np.empty((nlev, nb, SEAM_BLOCK), np.float32)
+        t = np.empty((nt, nb, SEAM_BLOCK), np.float32)
+        ordinary = np.array([1, 2, UNDEF, 3, 4], np.float32)
+        with np.errstate(over="ignore"):
+            for b, (ta, tb) in enumerate(order):
+                (la, ta), (lb, tb) = (ta if isinstance(ta, tuple) else (ta, ta)), (tb if isinstance(tb, tuple) else (tb, tb))
+                if la is None:  # the upper seam alone
+                    col, ta = [UNDEF, UNDEF, UNDEF, lb, np.nextafter(_F(lb), INF)], tb
+                else:
+                    col = [np.nextafter(_F(la), -INF), la, UNDEF, lb, np.nextafter(_F(lb), INF)]
+                c[:, b], t[:, b] = np.array(col, np.float32)[:, None], np.array([ta, tb, ta], np.float32)[:, None]
+        for b in range(len(order), nb):
+            c[:, b], t[:, b] = ordinary[:, None], np.array([2, 3, 2], np.float32)[:, None]
+        b = len(order)
+        t[:, b, :] = UNDEF
+        t[1, b, ::3] = np.nan
+        if log:
+            t[2, b, ::5] = -1.0
+        c[:, b + 1, 8:12] = np.nan  # a lane of four cells (four lanes of one) whose coordinates are all NaN: level 0 is flagged ALL_DEFINED,
+        c[1:, b + 1, 16:20] = UNDEF  # so there the NaN is a stored value that is not usable; and one that is undef below a NaN
+        c[0, b + 1, 16:20] = np.nan
+        c[:, b + 2, 5] = np.array([DENORM_MIN if log else -np.inf, np.inf, UNDEF, DENORM_MIN if log else -np.inf, np.inf], np.float32)
+        c, t = c.reshape(nlev, -1), t.reshape(nt, -1)
+        i = np.arange(nb * SEAM_BLOCK)
+        c[1, i % 37 == 11] = UNDEF  # a few cells of every wave lose their lower pair
+        t[2, i % 41 == 7] = UNDEF  # and a few targets are not usable: NaN to the wave's reduction
+        t[2, i % 41 == 19] = np.nan
+        base = dict(family="vregrid", kind="field", method=rule, klass="seam", undef=UNDEF, flags=flags, fields=fields, base=label, blocks=order,
+                    coord=c.reshape(nlev, ny, nx), fdef_c=np.array([ALL_DEFINED] + [SOME_DEFINED] * (nlev - 1), np.int32), tcoord=t.reshape(nt, ny, nx), fdef_t=np.full(nt, SOME_DEFINED, np.int32))
+        for v in base.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        out.append(base)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def vregrid_seam_cases():
+    """Every (from, outside) on the two seam bases, each with the method of its rule."""
+    out = []
+    for base in vregrid_seam_bases():
+        for m, f, o in VREGRID_COMBOS:
+            if m == base["method"]:
+                case = {k: v for k, v in base.items() if k not in ("tcoord", "fdef_t")}
+                case.update(label=base["base"].replace("-%d" % SEAM_BLOCK, "-%s.%s.%s-%d" % (m, f, o, SEAM_BLOCK), 1),
+                            extras=dict(tcoord=base["tcoord"], fdef_t=base["fdef_t"], method=m, from_=f, outside=o))
+                out.append(case)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ vregrid: columns by hand
+# Rule 5 of mifc_vregrid_* (include/mifc.h) where the compares are at their ends, and rule 1 of the `levels` form (c_k =
+# levels[k], the sign of a zero included).  Each column: coordinate, targets, and per `outside` the index of the level whose
+# value is expected (None: undef); the values are x_k = k + 1.  The same in both directions.
+HAND_COLUMNS = [
+    # infinite extremes: ct < -inf and ct > +inf are false, the hole leaves no bracket
+    dict(c=[-np.inf, UNDEF, np.inf], t=[5.0, -np.inf, np.inf, -FLT_MAX], undef=[None] * 4, clamp=[None] * 4),
+    # a target of +-inf beyond finite extremes
+    dict(c=[1, 2, 3], t=[np.inf, -np.inf], undef=[None, None], clamp=[2, 0]),
+    dict(c=[3, 2, 1], t=[np.inf, -np.inf], undef=[None, None], clamp=[0, 2]),
+    dict(c=[-FLT_MAX, 0, FLT_MAX], t=[np.inf, -np.inf], undef=[None, None], clamp=[2, 0]),
+    # extremes tied between +0 and -0 at different levels: the lowest index
+    dict(c=[-0.0, 3, 0.0, 7], t=[-1.0, -DENORM_MIN], undef=[None, None], clamp=[0, 0]),
+    dict(c=[0.0, 3, -0.0, 7], t=[-1.0, -DENORM_MIN], undef=[None, None], clamp=[0, 0]),
+    dict(c=[-5, 0.0, -3, -0.0], t=[1.0, DENORM_MIN], undef=[None, None], clamp=[1, 1]),
+    dict(c=[-5, -0.0, -3, 0.0], t=[1.0, DENORM_MIN], undef=[None, None], clamp=[1, 1]),
+    # a target equal to cmin / cmax that holes left without a bracket: not beyond, so undef
+    dict(c=[1, UNDEF, 3], t=[1.0, 3.0, 0.5, 3.5], undef=[None] * 4, clamp=[None, None, 0, 2]),
+    dict(c=[-0.0, UNDEF, DENORM_MIN], t=[0.0, DENORM_MIN, -DENORM_MIN, 2 * float(DENORM_MIN)], undef=[None] * 4, clamp=[None, None, 0, 2]),
+]
+
+
+def vregrid_hand_case(from_, outside):
+    """The hand columns side by side as one `field` case (ny = 1), and the expected output (1, nt, 1, ncolumns)."""
+    nlev, nt, n = max(len(h["c"]) for h in HAND_COLUMNS), max(len(h["t"]) for h in HAND_COLUMNS), len(HAND_COLUMNS)
+    c, t = np.full((nlev, 1, n), UNDEF, np.float32), np.full((nt, 1, n), UNDEF, np.float32)
+    x = np.broadcast_to(np.arange(1, nlev + 1, dtype=np.float32).reshape(1, nlev, 1, 1), (1, nlev, 1, n)).copy()
+    want = np.full((1, nt, 1, n), UNDEF, np.float32)
+    for i, h in enumerate(HAND_COLUMNS):
+        c[:len(h["c"]), 0, i], t[:len(h["t"]), 0, i] = np.array(h["c"], np.float32), np.array(h["t"], np.float32)
+        for j, k in enumerate(h[outside]):
+            want[0, j, 0, i] = UNDEF if k is None else k + 1
+    case = dict(label="vregrid-hand-%s-%s" % (from_, outside), family="vregrid", kind="field", method="linear", klass="hand", undef=UNDEF, fields=x,
+                flags=np.full((1, nlev), SOME_DEFINED, np.int32), coord=c, fdef_c=np.full(nlev, SOME_DEFINED, np.int32),
+                extras=dict(tcoord=t, fdef_t=np.full(nt, SOME_DEFINED, np.int32), method="linear", from_=from_, outside=outside))
+    return case, want
+
+
+def vregrid_zero_level_case(from_="first"):
+    """`levels` form: c_k = levels[k] with the sign of a zero kept.  From the level -0 the target -0 has the weight
+    (-0 - -0) / (1 - -0) = +0, and -0 + (+0) * (5 - -0) is +0; from a level +0 it would be -0 + (-0) * 5 = -0."""
+    x = np.array([-0.0, 5.0], np.float32).reshape(1, 2, 1, 1) * np.ones((1, 1, 1, 3), np.float32)
+    t = np.array([-0.0, 0.0, 1.0], np.float32).reshape(1, 1, 3)
+    case = dict(label="vregrid-zero-level-" + from_, family="vregrid", kind="levels", method="linear", klass="hand", undef=UNDEF, fields=x,
+                flags=np.full((1, 2), SOME_DEFINED, np.int32), levs=np.array([-0.0, 1.0], np.float32),
+                extras=dict(tcoord=t, fdef_t=np.array([SOME_DEFINED], np.int32), method="linear", from_=from_, outside="undef"))
+    return case, np.array([0.0, 0.0, 5.0], np.float32).reshape(1, 1, 1, 3)  # (the target +0: (+0 - -0) / 1 = +0 as well)
+
+
 # ------------------------------------------------------------------------------------------------ the restatement of a case
 def restate(case, mods=None, prefilter=None):
     """(out, flags_out) of the case by the family's restatement.  mods: the restatement modules to use instead (the CPU
     test's variants), a dict by family.  prefilter: vinterp only, see vinterp_restate.interpolate."""
-    m = dict(vinterp=vi, vlayer=vl, vderiv=vd, vcumul=vc, pvort=pv)
+    m = dict(vinterp=vi, vlayer=vl, vderiv=vd, vcumul=vc, pvort=pv, vregrid=vg)
     m.update(mods or {})
     family, kind, undef, ex = case["family"], case["kind"], case["undef"], case["extras"]
     x, fl = case["fields"], case["flags"]
+    if family == "vregrid":
+        how = (vg.LOG if ex["method"] == "log" else vg.LINEAR, vg.FROM_LAST if ex["from_"] == "last" else vg.FROM_FIRST,
+               vg.OUTSIDE_CLAMP if ex["outside"] == "clamp" else vg.OUTSIDE_UNDEF)
+        kw = {} if prefilter is None else dict(prefilter=prefilter)
+        if kind == "hybrid":
+            return m[family].hlevels(x, case["ps"], *case["ab"], ex["tcoord"], *how, fl, case["fdef_c"], ex["fdef_t"], undef, **kw)
+        if kind == "field":
+            return m[family].coord_fields(x, case["coord"], ex["tcoord"], *how, fl, case["fdef_c"], ex["fdef_t"], undef, **kw)
+        return m[family].levels(x, case["levs"], ex["tcoord"], *how, fl, ex["fdef_t"], undef, **kw)
     if family == "vinterp":
         method = vi.LOG if case["method"] == "log" else vi.LINEAR
         if kind == "hybrid":
@@ -514,7 +812,7 @@ def widened(case, times):
             out[k] = tile(case[k])
     ex = dict(case["extras"])
     for k, v in ex.items():
-        if isinstance(v, np.ndarray) and v.ndim == 2:
+        if isinstance(v, np.ndarray) and (v.ndim == 2 or k == "tcoord"):
             ex[k] = tile(v)
         elif k == "base":
             ex[k] = [None if b is None else tile(b) for b in v]

@@ -23,6 +23,8 @@ import vcumul_restate as vc
 import vderiv_restate as vd
 import vinterp_restate as vi
 import vlayer_restate as vl
+import vregrid_restate as vg
+from test_vregrid_cpu import header_run, shim  # noqa: F401  (the rules header of vregrid through the host compiler)
 
 A, N, S = cr.ALL_DEFINED, cr.NONE_DEFINED, cr.SOME_DEFINED
 U = cr.UNDEF
@@ -51,6 +53,8 @@ def finite_inputs(case):
                 cell &= np.isfinite(a)
     if family in ("vinterp", "vlayer"):
         return (lev.all(axis=0) & cell)[None, None]
+    if family == "vregrid":
+        return (lev.all(axis=0) & cell)[None, None] & np.isfinite(case["extras"]["tcoord"])[None]
     if family == "vcumul":
         order = slice(None) if case["extras"]["from_"] == "first" else slice(None, None, -1)
         walked = np.zeros_like(lev)
@@ -95,10 +99,13 @@ def test_cases_reach_what_they_are_meant_to_reach(family, klass):
         assert s["finite"] >= 0.30, (case["label"], s)
         if klass == "huge":
             assert s["big"] >= 0.01, (case["label"], s)
-            if family != "vinterp":  # see the module docstring
+            if family not in ("vinterp", "vregrid"):  # see the module docstring (vregrid: the same result, or a copy of a level)
                 assert s["inf"] >= 0.01, (case["label"], s)
         if klass == "tiny":
             assert s["subnormal"] >= 0.05, (case["label"], s)
+        if family == "vregrid":  # at most half holes
+            out, _ = cr.expected(case)
+            assert is_undef(out, case["undef"]).mean() <= 0.5, case["label"]
 
 
 def test_the_shapes_and_ingredients_of_the_cases():
@@ -224,7 +231,7 @@ class _NarrowNumpy:
 
 @contextlib.contextmanager
 def float_intermediates():
-    mods = (vi, vl, vd, vc, pv)
+    mods = (vi, vl, vd, vc, pv, vg)
     try:
         for m in mods:
             m.np = _NarrowNumpy()
@@ -253,6 +260,9 @@ def test_the_narrowing_variant_is_the_restatement_where_nothing_leaves_the_float
         case["method"] = "weighted"
     elif family == "vcumul":
         case.update(method="linear", extras=dict(from_="last"))
+    elif family == "vregrid":
+        planes = np.broadcast_to(np.array([0.5, 1.5, 2.0], np.float32).reshape(3, 1, 1), (3, ny, nx)).copy()
+        case.update(method="linear", extras=dict(tcoord=planes, fdef_t=np.full(3, S, np.int32), method="linear", from_="last", outside="clamp"))
     else:
         one = np.ones((ny, nx), np.float32)
         case.update(method="centred", fields=x, extras=dict(xmapr=2 * one, ymapr=2 * one, fcoriolis=one, scale=1.0))
@@ -390,6 +400,228 @@ def test_a_target_is_bit_equal_to_a_usable_coordinate_in_every_vinterp_case():
             assert np.isin(c[usable & np.isfinite(c)].view(np.uint32), list(bits)).any(), case["label"]
 
 
+# ---------------------------------------------------------------------------------------------- vregrid: targets, interval, clamp
+def vregrid_bases():
+    """One case per base (set of arrays): its first combination."""
+    seen = {}
+    for klass in cr.CLASSES:
+        for case in cr.cases("vregrid", klass):
+            seen.setdefault(case["base"], case)
+    return list(seen.values())
+
+
+def test_vregrid_every_kind_of_target_is_in_every_base_and_every_combination_is_run():
+    bases = vregrid_bases()
+    assert len(bases) == 7 * 3 + 2
+    for case in bases:
+        ex, label = case["extras"], case["base"]
+        t, what = ex["tcoord"], case["tkind"]
+        log = case["method"] == "log"
+        c, usable = cr.coordinate_of(case)
+        usable = usable & ~np.isnan(c)
+        assert all((what == j).mean() > 0.02 for j in range(len(cr.TARGET_KINDS))), label
+        assert set(np.unique(ex["fdef_t"])) == {A, S}, label
+        for flag in (A, S):  # a stored 1e35 under both flag values
+            assert (t[ex["fdef_t"] == flag] == U).any(), label
+        with np.errstate(invalid="ignore"):
+            # on a level: bit for bit; and some column has c_k == c_k+1 with a target on it
+            on = what == 0
+            assert (np.isin(t.view(np.uint32), c[usable].view(np.uint32)) & on).mean() > 0.1, label
+            equal = usable[:-1] & usable[1:] & (c[:-1] == c[1:])
+            assert equal.any() or log or case["kind"] == "hybrid", label  # (the LOG rule and the hybrid levels draw no equal neighbours)
+            assert ((t[:, None] == c[None, :-1]) & equal[None]).any() or equal.mean() < 0.002, label
+            # beyond both extremes of the column
+            cmin, cmax = np.where(usable, c, INF).min(axis=0), np.where(usable, c, -INF).max(axis=0)
+            assert ((t < cmin) & (what == 2)).mean() > 0.02 and ((t > cmax) & (what == 2)).mean() > (-1 if "levels-log" in label else 0.02), label  # (LEVELS_LOG ends on +inf)
+            for v in (0.0, DEN, -DEN, FLT_MAX, -FLT_MAX, INF, -INF, cr.UNDEF_BELOW, cr.UNDEF_ABOVE):
+                assert (t == F(v)).any(), (label, v)
+            assert np.isnan(t).any() and (np.signbit(t) & (t == 0)).any(), label
+            if log:
+                assert (t == F(-1.5)).any() and ((t <= 0) & (what != 4)).mean() < 0.25, label  # (half of 2^-149, below LEVELS_LOG, is 0)
+        combos = {(c2["extras"]["method"], c2["extras"]["from_"], c2["extras"]["outside"]) for klass in cr.CLASSES for c2 in cr.cases("vregrid", klass) if c2["base"] == label}
+        nlev = case["fields"].shape[1]
+        assert combos == {cb for cb in cr.VREGRID_COMBOS if log or cb[0] == "linear" or cr.log_runs_on_a_linear_base(case["kind"], nlev, cb[2])}, label
+        # LOG on a base of the LINEAR rule is left out exactly where more than half of its outputs would be holes (its
+        # coordinates cross zero): the combinations that run are held to a half by the test above, the others exceed it
+        for cb in cr.VREGRID_COMBOS:
+            if cb not in combos:
+                out, _ = cr.restate(dict(case, extras=dict(ex, method=cb[0], from_=cb[1], outside=cb[2])))
+                assert is_undef(out, case["undef"]).mean() > 0.5, (label, cb)
+    # per class one base takes two passes in each layout
+    for klass in cr.CLASSES:
+        nts = {(c2["fields"].shape[3] % 4 == 0, c2["extras"]["tcoord"].shape[0]) for c2 in cr.cases("vregrid", klass)}
+        assert (True, cr.VREGRID_TB[4] + 1) in nts and (False, cr.VREGRID_TB[1] + 1) in nts, klass
+
+
+def vregrid_filter(case, v, mistake=None):
+    c, usable = cr.coordinate_of(case)
+    ex = case["extras"]
+    return vg.wave_interval_filter(c, usable, ex["tcoord"], vg.LOG if ex["method"] == "log" else vg.LINEAR, ex["fdef_t"], case["undef"], v=v,
+                                   tb=cr.VREGRID_TB[v], mistake=mistake)
+
+
+def test_vregrid_the_wave_interval_as_the_kernel_has_it_changes_nothing():
+    """The model of the skip -- [min, max] per wave from [+inf, -inf], a NaN passed by, both compares closed -- turns away
+    no pair that a cell brackets: on every range case and seam case, in both layouts, the filtered restatement is the
+    restatement.  In the seam cases it does skip."""
+    mine = [c for klass in cr.CLASSES for c in cr.cases("vregrid", klass)] + cr.vregrid_seam_cases()
+    for case in mine:
+        for v in (4, 1):
+            look, skipped = vregrid_filter(case, v)
+            assert not differs(cr.restate(case, prefilter=look), cr.expected(case)), (case["label"], v)
+            assert skipped > 0 or case["klass"] != "seam", (case["label"], v)
+
+
+LOSING_FILTERS = [m for m in vg.FILTER_MISTAKES if m != "reductions start from +-FLT_MAX"]
+
+
+def test_vregrid_a_wave_interval_that_parts_from_the_cell_compare_loses_a_target_in_every_seam_case():
+    """A strict compare on either side, a reduction that flushes subnormals (the targets' or the pairs', one without the
+    other), a min / max that hands a NaN on: each changes at least one output of every seam case, in both layouts.  Making
+    either side of the kernel's skip test strict, or building the reductions from an instruction that flushes or that
+    returns NaN, fails tests/test_gpu_column_range.py on these cases."""
+    for case in cr.vregrid_seam_cases():
+        for v in (4, 1):
+            for mistake in LOSING_FILTERS:
+                look, _ = vregrid_filter(case, v, mistake)
+                assert differs(cr.restate(case, prefilter=look), cr.expected(case)), (case["label"], v, mistake)
+
+
+def test_vregrid_reductions_started_from_flt_max_only_widen_the_interval():
+    """A minimum started from +FLT_MAX instead of +inf can only come out smaller, a maximum from -FLT_MAX only larger: both
+    intervals of the skip test grow, a pair that was looked at still is, and no output can change -- on no case at all.
+    What the wrong start costs is pairs that are looked at in vain (never more skipped than with the right start); no test
+    of outputs can see it, and none here claims to."""
+    for case in [c for klass in cr.CLASSES for c in cr.cases("vregrid", klass)] + cr.vregrid_seam_cases():
+        for v in (4, 1):
+            look, skipped = vregrid_filter(case, v, "reductions start from +-FLT_MAX")
+            assert not differs(cr.restate(case, prefilter=look), cr.expected(case)), (case["label"], v)
+            assert skipped <= vregrid_filter(case, v)[1], (case["label"], v)
+
+
+def test_vregrid_seam_cases_end_their_pairs_on_the_wave_extremes():
+    """In every seam block the smallest target of the wave is the upper end of the one pair that brackets it and the largest
+    the lower end of its pair; both are found with a defined result in most cells; the block of unusable targets is undef."""
+    for base in cr.vregrid_seam_bases():
+        c, t = base["coord"], base["tcoord"]
+        nb = len(base["blocks"])
+        for b, (ta, tb) in enumerate(base["blocks"]):
+            with np.errstate(invalid="ignore"):
+                usable_t = np.where((t[:, b] == U) | np.isnan(t[:, b]), np.nan, t[:, b])
+                lo, hi = np.nanmin(usable_t), np.nanmax(usable_t)
+                assert hi == c[3, b].min() == c[3, b].max(), (base["base"], b)  # the lower end of the pair (3, 4)
+                if ta is not None:  # the upper end of the pair (0, 1), where a hole has not taken it
+                    assert lo == c[1, b][c[1, b] != U].max() == c[1, b][c[1, b] != U].min() and (c[1, b] != U).mean() > 0.9, (base["base"], b)
+        for case in cr.vregrid_seam_cases():
+            if case["base"] != base["base"]:
+                continue
+            out, fd = cr.expected(case)
+            found = out[0] != U
+            assert found[:2, :nb].mean() > 0.8 and not found[:, nb].any() and (fd == S).all(), case["label"]
+            if case["method"] == "linear":  # the cell whose pair is (-inf, +inf): inf / inf (LOG: (2^-149, +inf), weight 0)
+                assert np.isnan(out[:, :, nb + 2, 5]).any(), case["label"]
+
+
+def test_vregrid_log_results_move_by_one_float_step_at_most_when_log_is_an_ulp_off():
+    """The allowance of MIFC_VINTERP_LOG on the range and seam cases, established as tests/test_vregrid_cpu.py does it for
+    the ordinary ones: with every double log() moved by one ulp -- up, down, each its own way -- no undef cell and no flag
+    changes, no result moves by more than one float step and at most 1 % of the compared results move at all."""
+    # each value its own way, but the same value always the same way: a device's log() is a function
+    coin = lambda v: (np.asarray(v, np.float64).view(np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(63) != 0  # noqa: E731
+    finite = lambda v, to: np.where(np.isfinite(np.log(v)), np.nextafter(np.log(v), to), np.log(v))  # noqa: E731  (log(inf) is inf on any device)
+    moves = {"up": lambda v: finite(v, np.inf), "down": lambda v: finite(v, -np.inf),
+             "mixed": lambda v: finite(v, np.where(coin(v), np.inf, -np.inf))}
+    worst, n = 0.0, 0
+    for case in [c for klass in cr.CLASSES for c in cr.cases("vregrid", klass)] + cr.vregrid_seam_cases():
+        if case["extras"]["method"] != "log":
+            continue
+        exp, efd = cr.expected(case)
+        for name, moved in moves.items():
+            got, gfd = cr.restate(case, dict(vregrid=_MovedLog(moved)))
+            assert np.array_equal(gfd, efd) and np.array_equal(got == U, exp == U), (case["label"], name)
+            d = (exp != U) & ~(np.isnan(got) & np.isnan(exp))
+            steps = np.abs(got.view(np.int32)[d].astype(np.int64) - exp.view(np.int32)[d].astype(np.int64))
+            assert steps.max() <= 1 and (steps != 0).mean() <= 0.01, (case["label"], name, int(steps.max()), float((steps != 0).mean()))
+            worst = max(worst, float((steps != 0).mean()))
+        n += 1
+    print("LOG cases %d, largest share of results moved by a log() one ulp off: %.4f %%" % (n, 100 * worst))
+    assert n == 3 * 12 + 4 + 28  # the LOG bases, the seam cases, LOG on the bases of the LINEAR rule
+
+
+class _MovedLog:
+    """vregrid_restate with another double logarithm."""
+
+    def __init__(self, log):
+        self.log = log
+
+    def hlevels(self, *a, **kw):
+        return vg.hlevels(*a, log=self.log, **kw)
+
+    def coord_fields(self, *a, **kw):
+        return vg.coord_fields(*a, log=self.log, **kw)
+
+    def levels(self, *a, **kw):
+        return vg.levels(*a, log=self.log, **kw)
+
+
+def same_or_neighbour(case, got, gfd, exp, efd, label):
+    """The compare of tests/test_gpu_vregrid.py without its import of torch: LINEAR bit for bit, LOG the neighbour rule."""
+    assert np.array_equal(gfd, efd), label
+    if case["extras"]["method"] == "linear":
+        assert not differs((got, gfd), (exp, efd)), label
+        return
+    und = is_undef(exp, case["undef"])
+    assert np.array_equal(is_undef(got, case["undef"]), und), label
+    d = ~und & ~(np.isnan(got) & np.isnan(exp))
+    steps = np.abs(got.view(np.int32)[d].astype(np.int64) - exp.view(np.int32)[d].astype(np.int64))
+    assert steps.size == 0 or (steps.max() <= 1 and (steps != 0).mean() <= 0.01), label
+
+
+@pytest.mark.parametrize("klass", cr.CLASSES + ("seam",))
+def test_vregrid_rules_header_on_the_range_and_seam_cases(shim, klass):  # noqa: F811
+    """mifc_vregrid_rules.h, the text the kernel is built from, compiled with the host compiler and walked cell by cell
+    (tests/host/vregrid_rules_driver.h) gives what the restatement gives on every range and seam case."""
+    for case in (cr.vregrid_seam_cases() if klass == "seam" else cr.cases("vregrid", klass)):
+        ex = case["extras"]
+        got, gfd = header_run(shim, cr.vregrid_plain(case), ex["method"], ex["from_"], ex["outside"])
+        exp, efd = cr.expected(case)
+        same_or_neighbour(case, got, gfd, exp, efd, case["label"])
+
+
+def test_vregrid_clamp_rule_at_the_ends_of_its_compares(shim):  # noqa: F811
+    """Rule 5 of mifc_vregrid_* by hand (column_range_cases.HAND_COLUMNS): infinite extremes (ct < -inf is false: undef), a
+    target of +-inf beyond finite extremes, extremes tied between +0 and -0 at different levels (the lowest index, in both
+    directions), a target equal to an extreme that holes left without a bracket (undef, not clamped) -- the restatement
+    and the rules header both give the hand-written result."""
+    for from_ in ("first", "last"):
+        for outside in ("undef", "clamp"):
+            case, want = cr.vregrid_hand_case(from_, outside)
+            out, fd = cr.restate(case)
+            assert np.array_equal(out.view(np.uint32), want.view(np.uint32)), (from_, outside, out, want)
+            got, gfd = header_run(shim, cr.vregrid_plain(case), "linear", from_, outside)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(gfd, fd), (from_, outside)
+    # the extremes themselves, as the walk in either direction leaves them: (kmin, kmax)
+    out = np.zeros(2, np.int32)
+    for col, want in (([-0.0, 3, 0.0, 7], (0, 3)), ([0.0, 3, -0.0, 7], (0, 3)), ([-5, 0.0, -3, -0.0], (0, 1)), ([-5, -0.0, -3, 0.0], (0, 1)),
+                      ([-INF, np.nan, INF], (0, 2)), ([INF, -INF, INF, -INF], (1, 0)), ([DEN, -DEN, DEN, -DEN], (1, 0)), ([FLT_MAX, INF, FLT_MAX], (0, 1))):
+        c = np.asarray(col, np.float32)
+        for descending in (0, 1):
+            shim.mifc_test_vregrid_extremes(c.ctypes.data, c.size, descending, out.ctypes.data)
+            assert tuple(out) == want, (col, descending, tuple(out))
+
+
+def test_vregrid_levels_form_keeps_the_sign_of_a_zero_level(shim):  # noqa: F811
+    """Rule 1: "mifc_vregrid_levels: c_k = levels[k]".  The sign of a zero level reaches the result through the weight."""
+    for from_ in ("first", "last"):
+        case, want = cr.vregrid_zero_level_case(from_)
+        out, fd = cr.restate(case)
+        assert np.array_equal(out.view(np.uint32), want.view(np.uint32)), (from_, out)
+        got, _ = header_run(shim, cr.vregrid_plain(case), "linear", from_, "undef")
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (from_, got)
+        plus = dict(case, levs=np.array([0.0, 1.0], np.float32))
+        assert np.signbit(cr.restate(plus)[0][0, 0, 0, 0]) and not np.signbit(out[0, 0, 0, 0])  # the level +0 gives -0: the case tells them apart
+
+
 # ---------------------------------------------------------------------------------------------- the header, by hand
 def column(*levels):
     """Values down one column as a (1, nlev, 1, 1) field batch."""
@@ -510,7 +742,7 @@ def test_header_hybrid_coordinate_in_float():
 def test_header_levels_form_is_the_field_form():
     """mifc_vderiv_levels: "c_k = levels[k], always defined": the same rules on a constant coordinate, the weights included."""
     for klass in cr.CLASSES:
-        for family in ("vderiv", "vcumul", "pvort"):
+        for family in ("vderiv", "vcumul", "pvort", "vregrid"):
             for c in cr.cases(family, klass):
                 if c["kind"] == "levels":
                     assert not differs(cr.restate(cr.as_field(c)), cr.expected(c)), c["label"]

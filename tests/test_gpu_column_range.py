@@ -1,5 +1,5 @@
-"""The column-walk families (mifc_vinterp_*, mifc_vlayer_*, mifc_vderiv_*, mifc_vcumul_*, mifc_pvort_*) at the ends of the
-float range on the GPU: every case of tests/column_range_cases.py through the library, compared with the numpy restatement
+"""The column-walk families (mifc_vinterp_*, mifc_vlayer_*, mifc_vderiv_*, mifc_vcumul_*, mifc_pvort_*, mifc_vregrid_*) at the
+ends of the float range on the GPU: every case of tests/column_range_cases.py through the library, compared with the numpy restatement
 by the family's own rule (the `compare` of the family's GPU test file): bit for bit, a NaN matching any NaN, flags equal;
 for the LOG methods the restatement's float or its neighbour, undef cells and flags exact.  What the cases hold and why
 they would show a flush to zero, a float intermediate or a bracket that loses a target is asserted on the CPU in
@@ -8,7 +8,10 @@ tests/test_column_range_cpu.py.
 Per case: device memory on the 16-byte grid, device memory one float past it (one cell per lane on the same data: not a
 bit may change), host memory in one band; per family one case widened along y through the host path with the family's
 MIFC_*_CHUNK_MIB at 1, which takes more than one band.  The inputs are unchanged after each call and the floats around a
-device output are intact."""
+device output are intact.
+
+mifc_vregrid_* takes four cells per lane only where MIFC_VREGRID_V asks for it: its tests set it to 4, so that the batch
+on the grid at width 68 runs in that layout (15 target planes per pass) and everything else one cell per lane (24)."""
 import numpy as np
 import pytest
 
@@ -18,6 +21,7 @@ import test_gpu_vcumul as tvc
 import test_gpu_vderiv as tvd
 import test_gpu_vinterp as tvi
 import test_gpu_vlayer as tvl
+import test_gpu_vregrid as tvg
 import vlayer_restate as vl
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +42,8 @@ def compare(case, got, gfd, exp, efd, label):
         tvd.compare(got, exp, gfd, efd, label)
     elif family == "vcumul":
         tvc.compare(got, exp, gfd, efd, tvc.vc.METHODS[case["method"]], label)
+    elif family == "vregrid":
+        tvg.compare(got, exp, gfd, efd, case["extras"]["method"], case["undef"], label)
     else:
         tpv.compare(got, exp, gfd, efd, label)
 
@@ -88,6 +94,16 @@ def call(ctx, case, where, out_shape, form=None):
         if "start" in ex:
             more.update(start=put(ex["start"]), base=[put(b) for b in ex["base"]])
         out, fd = getattr(tvc.front(), "vcumul_" + name)(ctx, f, *head, case["method"], ex["from_"], **more, **kw)
+    elif family == "vregrid":
+        out, fd = getattr(tvg.front(), "vregrid_" + name)(ctx, f, *head, put(ex["tcoord"]), method=ex["method"], from_=ex["from_"], outside=ex["outside"],
+                                                           fdef_tcoord=ex["fdef_t"], **kw)
+        nx, nt = case["fields"].shape[3], ex["tcoord"].shape[0]
+        seen = tvg.front().last_vregrid_form(ctx)
+        want = {"method": ex["method"], "from": ex["from_"], "outside": ex["outside"], "coord": kind}
+        if form and "v" in form and device:  # MIFC_VREGRID_V = 4 is set: four cells per lane on the grid
+            v4 = 4 if nx % 4 == 0 and PAD[where] % 4 == 0 else 1
+            want.update(v=v4, tb=cr.VREGRID_TB[v4], passes=-(-nt // cr.VREGRID_TB[v4]))
+        assert {k: seen[k] for k in want} == want, (case["label"], where, seen, want)
     else:
         out, fd = getattr(tpv.front(), "pvort_" + name)(ctx, f[0], f[1], f[2], *head, put(ex["xmapr"]), put(ex["ymapr"]), put(ex["fcoriolis"]),
                                                         case["method"], scale=ex["scale"], **kw)
@@ -116,11 +132,20 @@ def check(ctx, case, where, form=None):
     return got, gfd
 
 
+def four_cells_per_lane(mifc_env, family):
+    """vregrid: ask for four cells per lane where the batch allows; the form that `call` then expects of a device call."""
+    if family != "vregrid":
+        return None
+    mifc_env("MIFC_VREGRID_V", 4)
+    return {"v": 4}
+
+
 @pytest.mark.parametrize("family,klass", GROUPS)
-def test_range_cases_in_device_and_host_memory(gpu_ctx, family, klass):
+def test_range_cases_in_device_and_host_memory(gpu_ctx, mifc_env, family, klass):
+    form = four_cells_per_lane(mifc_env, family)
     for case in cr.cases(family, klass):
-        on_grid, fd = check(gpu_ctx, case, "aligned")
-        off_grid, ofd = check(gpu_ctx, case, "offset")
+        on_grid, fd = check(gpu_ctx, case, "aligned", form)
+        off_grid, ofd = check(gpu_ctx, case, "offset", form)
         # one cell per lane on the same data (LOG as well: the same log() of the same doubles)
         assert ((on_grid.view(np.uint32) == off_grid.view(np.uint32)) | (np.isnan(on_grid) & np.isnan(off_grid))).all(), (case["label"], "off the grid")
         assert np.array_equal(fd, ofd), case["label"]
@@ -138,6 +163,41 @@ def test_vinterp_where_the_interval_of_a_wave_ends_on_a_target(gpu_ctx):
         assert ((on_grid.view(np.uint32) == off_grid.view(np.uint32)) | (np.isnan(on_grid) & np.isnan(off_grid))).all(), (case["label"], "off the grid")
         assert np.array_equal(fd, ofd), case["label"]
         check(gpu_ctx, case, "host")
+
+
+def test_vregrid_where_the_interval_of_a_wave_ends_on_a_target(gpu_ctx, mifc_env):
+    """The seam cases of the wave skip (column_range_cases.vregrid_seam_cases): whole waves whose smallest / largest usable
+    target is the end of the one pair that brackets it, the ends at +-0, +-2^-149, +-FLT_MIN, +-FLT_MAX and +-inf; a wave
+    without a usable target, a lane without levels, a pair from -inf to +inf.  tests/test_column_range_cpu.py shows on a
+    model of the skip that a strict compare on either side, a flush in one of the reductions or a NaN that comes through
+    one changes these cases, in the layout of four cells per lane (on the grid) and of one (off it)."""
+    form = four_cells_per_lane(mifc_env, "vregrid")
+    for case in cr.vregrid_seam_cases():
+        on_grid, fd = check(gpu_ctx, case, "aligned", form)
+        off_grid, ofd = check(gpu_ctx, case, "offset", form)
+        assert ((on_grid.view(np.uint32) == off_grid.view(np.uint32)) | (np.isnan(on_grid) & np.isnan(off_grid))).all(), (case["label"], "off the grid")
+        assert np.array_equal(fd, ofd), case["label"]
+        check(gpu_ctx, case, "host")
+    mifc_env("MIFC_VREGRID_V", None)  # and as the library chooses by itself
+    for case in cr.vregrid_seam_cases():
+        check(gpu_ctx, case, "aligned")
+
+
+def test_vregrid_clamp_rule_and_zero_level_by_hand(gpu_ctx):
+    """The hand-written columns of rule 5 (infinite extremes, targets of +-inf, extremes tied between +0 and -0, a target on
+    an extreme that holes left without a bracket) and the `levels` form with a level of -0, whose sign reaches the result."""
+    for from_ in ("first", "last"):
+        for outside in ("undef", "clamp"):
+            case, want = cr.vregrid_hand_case(from_, outside)
+            efd = cr.restate(case)[1]
+            for where in ("aligned", "offset", "host"):
+                got, gfd = call(gpu_ctx, case, where, want.shape)
+                assert same_bits(got, want) and np.array_equal(gfd.reshape(efd.shape), efd), (case["label"], where, got, want, gfd, efd)
+        case, want = cr.vregrid_zero_level_case(from_)
+        efd = cr.restate(case)[1]
+        for where in ("aligned", "host"):
+            got, gfd = call(gpu_ctx, case, where, want.shape)
+            assert same_bits(got, want) and np.array_equal(gfd.reshape(efd.shape), efd), (case["label"], where, got, want, gfd, efd)
 
 
 @pytest.mark.parametrize("family", cr.FAMILIES)
@@ -166,7 +226,7 @@ def test_the_coordinate_forms_of_one_problem_give_the_same_bits(gpu_ctx, family)
 # The whole problem of the widened case -- its planes of 180 rows, before any padding -- is larger than the MiB (asserted), so
 # a call that honours the budget takes at least two bands; where the entry reports its launches (vcumul, pvort) that is read
 # back as well.  The level-batch entries of vinterp, vlayer and vderiv report no band count.
-BAND_CASES = {"vinterp": ("huge", 1), "vlayer": ("tiny", 2), "vderiv": ("huge", 1), "vcumul": ("tiny", 1), "pvort": ("huge", 3)}
+BAND_CASES = {"vinterp": ("huge", 1), "vlayer": ("tiny", 2), "vderiv": ("huge", 1), "vcumul": ("tiny", 1), "pvort": ("huge", 3), "vregrid": ("tiny", 11)}
 
 
 @pytest.mark.parametrize("family", cr.FAMILIES)
@@ -177,7 +237,7 @@ def test_host_call_in_more_than_one_band(gpu_ctx, mifc_env, family):
     assert wide["kind"] == "field" and wide["fields"].shape[2] == 180, wide["label"]
     exp, efd = cr.restate(wide)
     arrays = [wide["fields"], wide["coord"], exp] + [a for v in wide["extras"].values() for a in (v if isinstance(v, list) else [v])
-                                                     if isinstance(a, np.ndarray) and a.ndim == 2]
+                                                     if isinstance(a, np.ndarray) and a.ndim >= 2]
     assert 4 * sum(a.size for a in arrays) > 2 ** 20, (wide["label"], "fits one band")
     got, gfd = call(gpu_ctx, wide, "host", exp.shape, form={"bands": None, "launches": None})
     compare(wide, got, gfd.reshape(efd.shape), exp, efd, (wide["label"], "bands"))
@@ -187,6 +247,9 @@ def test_host_call_in_more_than_one_band(gpu_ctx, mifc_env, family):
     if family == "vcumul":  # two fields: one launch per band
         seen = tvc.front().last_vcumul_form(gpu_ctx)
         assert seen["launches"] >= 2, seen
+    if family == "vregrid":  # 25 target planes: two passes per band
+        seen = tvg.front().last_vregrid_form(gpu_ctx)
+        assert seen["passes"] == 2 and seen["launches"] >= 4, seen
     # the bands against the one-launch device call itself
     dev, dfd = call(gpu_ctx, wide, "aligned", exp.shape)
     assert ((got.view(np.uint32) == dev.view(np.uint32)) | (np.isnan(got) & np.isnan(dev))).all() and np.array_equal(gfd, dfd), (wide["label"], "bands against the device call")
@@ -214,6 +277,10 @@ def _all_computed(family):
         case["fields"] = np.full((2, nlev, ny, nx), big, np.float32)
         case["coord"] = coord * np.float32(4)
         case.update(method="linear", extras=dict(from_="first"))
+    elif family == "vregrid":  # as vinterp; the second plane lies beyond the column and is clamped to a level of +inf
+        case["fields"] = np.broadcast_to(np.float32(np.inf) * sign, (2, nlev, ny, nx)).copy()
+        planes = np.broadcast_to(np.array([0.25, 7.0], np.float32).reshape(2, 1, 1), (2, ny, nx)).copy()
+        case.update(method="linear", extras=dict(tcoord=planes, fdef_t=np.full(2, A, np.int32), method="linear", from_="last", outside="clamp"))
     else:
         z = np.zeros((2, nlev, ny, nx), np.float32)
         case["fields"] = np.concatenate([z, x[:1]])

@@ -230,6 +230,40 @@ def test_fuzz_programs_equal_the_restatement(gpu_ctx, seed, device):
     agree(got, fd, want, wfd.reshape(np.asarray(fd).shape), seed)  # every cell, bit for bit (a NaN matches a NaN), every flag
 
 
+RANGE_FUZZ = [(klass, seed) for klass in ("huge", "tiny") for seed in fr.FUZZ_RANGE_SEEDS[klass]]
+
+
+@pytest.mark.parametrize("klass,seed", RANGE_FUZZ)
+def test_fuzz_programs_of_the_range_classes_equal_the_restatement(gpu_ctx, klass, seed):
+    """The `huge` and `tiny` fuzz cases (tests/test_fexpr_cpu.py holds what they reach: overflow, underflow, NaN, an
+    intermediate that equals 1e35 by arithmetic): device memory on the 16-byte grid, one float off it (the scalar form) and
+    host memory; every cell bit for bit, every flag."""
+    case = fr.fuzz_case(seed, klass=klass)
+    prog = fexpr.Program.from_code(case["code"].tolist(), case["consts"], case["out_regs"], len(case["fields"]), len(case["planes"]),
+                                   len(case["level_scalars"]))
+    want, wfd = restated(prog, case["fields"], case["planes"], case["level_scalars"], case["undef"])
+    for where, put in (("device", dev), ("off the grid", lambda a: dev(a, 1)), ("host", np.ascontiguousarray)):
+        got, fd = fexpr.evaluate(gpu_ctx, prog, [put(f) for f in case["fields"]], [put(p) for p in case["planes"]], case["level_scalars"], undef=case["undef"])
+        agree(got, fd, want, wfd.reshape(np.asarray(fd).shape), (klass, seed, where))
+        form = fexpr.last_fexpr_form(gpu_ctx)["form"]
+        if where == "off the grid" or (where == "device" and len(case["out_regs"]) == 1):  # (a stacked second output is off the grid by itself)
+            assert form == ("scalar" if where == "off the grid" else "vector"), (klass, seed, where, form)
+
+
+@pytest.mark.parametrize("name", fr.RANGE_TABLE_OPS)
+def test_one_operation_over_the_range_operands(gpu_ctx, name):
+    """One operation per program over every pair (for select and mask: triple) of the range operands: zeros of both signs,
+    +-2^-149, FLT_MIN, +-FLT_MAX, 1e35 and both its neighbours, NaN, the infinities.  The interpreter computes and selects
+    undef afterwards; the restatement tests first.  Bit for bit, in the vector and the scalar form and from host memory."""
+    a, b, c = fr.range_operand_fields()
+    table = fr.range_table_program(name)
+    prog = fexpr.Program.from_code(table["code"].tolist(), table["consts"], table["out_regs"], 3, 0, 0)
+    want, wfd = restated(prog, [a, b, c])
+    for where, put in (("device", dev), ("off the grid", lambda x: dev(x, 1)), ("host", np.ascontiguousarray)):
+        got, fd = fexpr.evaluate(gpu_ctx, prog, [put(a), put(b), put(c)])
+        agree(got, fd, want, wfd.reshape(np.asarray(fd).shape), (name, where))
+
+
 def ulps(a, b):
     """The distance of two float32 arrays in units in the last place (zeros of both signs are one number, infinity is the
     number after the largest finite one); NaN against NaN is 0, NaN against a number is huge."""

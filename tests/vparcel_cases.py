@@ -28,16 +28,20 @@ def _qsat(T, p):
     return np.where(ok, q, F(1e-3)).astype(F)
 
 
-def make(nlev, ny, nx, from_, source, seed=0):
+def make(nlev, ny, nx, from_, source, seed=0, factor=1.0):
+    """factor: every pressure of the case (ps, alevel, the fields form's p, the levels, p_src) times this number, q_src from
+    the saturation value at the scaled pressure (tests/vparcel_range_cases.py); 1: the cases as they always were."""
     rng = np.random.default_rng(1000 * nlev + 10 * ny + nx + seed)
+    k = F(factor)
     top = 300.0 if nlev <= 3 else 240.0  # (the coldest, driest parcels leave the saturation table below it)
     P = (1000.0 * (top / 1000.0) ** (np.arange(nlev) / (nlev - 1))).astype(F)  # position order: the surface first
     bl = ((P / F(1000.0)) ** 2).astype(F)
     al = (P - F(1000.0) * bl).astype(F)
     al[0], bl[0] = F(0.0), F(1.0)
+    P, al = (P * k).astype(F), (al * k).astype(F)
     x = np.broadcast_to(np.arange(nx)[None, :], (ny, nx))
     y = np.broadcast_to(np.arange(ny)[:, None], (ny, nx))
-    ps = (985.0 + 3.0 * (x % 11) + 1.7 * y + rng.uniform(-0.5, 0.5, (ny, nx))).astype(F)
+    ps = ((985.0 + 3.0 * (x % 11) + 1.7 * y + rng.uniform(-0.5, 0.5, (ny, nx))).astype(F) * k).astype(F)
     p = vp.hybrid_pressure(ps, al, bl, A)
     Ts = (250.0 + 56.0 *((x * 7 + y * 3) % nx) / max(nx - 1, 1) + rng.uniform(-0.4, 0.4, (ny, nx))).astype(F)
     g = (0.10 + 0.17 * ((x * 5 + y) % 7) / 6.0).astype(F)  # d ln T / d ln p: 0.286 is the dry adiabat
@@ -52,7 +56,7 @@ def make(nlev, ny, nx, from_, source, seed=0):
     c = {"name": "n%d_%dx%d_%s_%s" % (nlev, ny, nx, from_, source), "nlev": nlev, "ny": ny, "nx": nx, "from": from_, "source": source}
     if source == "planes":
         c["src_level"] = None
-        c["p_src"] = np.where((x + y) % 3 == 0, ps + F(4.0), ps * F(0.97)).astype(F)  # below the ground / between two levels
+        c["p_src"] = np.where((x + y) % 3 == 0, ps + F(4.0) * k, ps * F(0.97)).astype(F)  # below the ground / between two levels
         c["t_src"] = (Ts + F(0.5)).astype(F)
         c["q_src"] = (rh * _qsat(c["t_src"], c["p_src"])).astype(F)
         js = -1

@@ -18,11 +18,13 @@ MISTAKES = ("last bracket under from first", "pair oriented by the walk", "clamp
 
 
 def regrid(fields, coord, coord_defined, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF, flags=None, fdef_tcoord=None, undef=UNDEF,
-           mistakes=(), log=np.log):
+           mistakes=(), log=np.log, prefilter=None):
     """fields float32 (nf, nlev, ny, nx); coord float32 (nlev, ny, nx) and coord_defined bool of the same shape (rule 1);
     tcoord float32 (nt, ny, nx); flags None (SOME_DEFINED) or (nf, nlev); fdef_tcoord None or (nt,).  Returns (out (nf, nt,
     ny, nx), flags_out int32 (nf, nt)).  log: the double logarithm of rule 4 (a test moves its results by an ulp).
-    mistakes: names from MISTAKES, not part of the definition."""
+    mistakes: names from MISTAKES, not part of the definition.  prefilter: None, or prefilter(k, t) -> bool (cells): the pair
+    (k, k + 1) is looked at for target t only where it holds (a model of the kernel's wave skip, wave_interval_filter below;
+    not part of the definition either)."""
     assert all(m in MISTAKES for m in mistakes), mistakes
     x = np.asarray(fields, np.float32)
     nf, nlev, ny, nx = x.shape
@@ -70,6 +72,8 @@ def regrid(fields, coord, coord_defined, tcoord, method, from_=FROM_FIRST, outsi
                 lo, hi = np.minimum(c[k], c[k + 1]), np.maximum(c[k], c[k + 1])  # a NaN comes through and fails both comparisons
                 lower = (lo < ct) if "open bracket end" in mistakes else (lo <= ct)
                 br = usable & cdef[k] & cdef[k + 1] & lower & (ct <= hi) & ~found
+                if prefilter is not None:
+                    br &= prefilter(k, t)
                 if not br.any():
                     continue
                 found |= br
@@ -129,6 +133,86 @@ def levels(fields, levs, tcoord, method, from_=FROM_FIRST, outside=OUTSIDE_UNDEF
     shape = np.shape(fields)[1:]
     c = np.broadcast_to(lv[:, None, None], shape).astype(np.float32)
     return regrid(fields, c, np.ones(shape, bool), tcoord, method, from_, outside, flags, fdef_tcoord, undef, **kw)
+
+
+# ---------------------------------------------------------------------------------------------- the wave's interval
+FILTER_MISTAKES = ("strict on the low side", "strict on the high side", "target reduction flushes subnormals", "pair reduction flushes subnormals",
+                   "reductions start from +-FLT_MAX", "a NaN comes through the reduction")
+
+
+def _flush(x):
+    x = np.asarray(x, np.float32)
+    tiny = np.finfo(np.float32).tiny
+    return np.where((x != 0) & (np.abs(x) < tiny), np.copysign(np.float32(0), x), x).astype(np.float32)
+
+
+def wave_interval_filter(coord, coord_defined, tcoord, method, fdef_tcoord=None, undef=UNDEF, v=1, tb=24, mistake=None):
+    """A model of the skip of vregrid_kernel (mi-fieldcalc_amd/csrc/mifc_vregrid.hip) as the `prefilter` of regrid, and the
+    number of (wave, pass, pair) triples it skips.  A wave is 64 lanes of v consecutive cells.  Per pass of tb target planes
+    the wave reduces [tmin, tmax] of its usable targets, from [+inf, -inf], a target that is not usable (NaN) passed by; the
+    lanes past the end of the batch hold no target.  Per pair of levels it reduces [lo, hi] of min / max (c_k, c_k+1) over its
+    cells, a cell without a usable pair counting as [+inf, -inf]; the lanes past the end walk cells 0 .. v - 1.  The pair is
+    looked at where lo <= tmax and hi >= tmin.  mistake: one of FILTER_MISTAKES."""
+    assert mistake is None or mistake in FILTER_MISTAKES, mistake
+    F = np.float32
+    c = np.asarray(coord, np.float32)
+    nlev = c.shape[0]
+    c = c.reshape(nlev, -1)
+    n = c.shape[1]
+    c = np.where(np.asarray(coord_defined, bool).reshape(nlev, n), c, F(np.nan))
+    tc = np.asarray(tcoord, np.float32)
+    nt = tc.shape[0]
+    tc = tc.reshape(nt, n).copy()
+    ft = [SOME_DEFINED] * nt if fdef_tcoord is None else list(np.asarray(fdef_tcoord).reshape(nt))
+    with np.errstate(invalid="ignore"):
+        for t in range(nt):
+            usable = is_defined(ft[t] == ALL_DEFINED, tc[t], np.float32(undef)) & ~np.isnan(tc[t])
+            if method == LOG:
+                usable &= tc[t] > 0
+            tc[t, ~usable] = np.nan
+    per_wave = 64 * v
+    first = np.arange(0, n, per_wave)
+    big = np.finfo(np.float32).max if mistake == "reductions start from +-FLT_MAX" else F(np.inf)
+    through = mistake == "a NaN comes through the reduction"
+    mn, mx = (np.minimum, np.maximum) if through else (np.fmin, np.fmax)  # np.minimum hands a NaN on, np.fmin passes it by
+
+    def reduce(op, rows, start):
+        """op over the rows (an (m, n) array) and over each wave's cells, started from `start`."""
+        lane = rows[0] if through else op(F(start), rows[0])
+        for r in rows[1:]:
+            lane = op(lane, r)
+        w = op.reduceat(lane, first)
+        return w if through else op(F(start), w)
+
+    with np.errstate(invalid="ignore"):
+        tmin, tmax = [], []
+        for t0 in range(0, nt, tb):
+            tmin.append(reduce(mn, tc[t0:t0 + tb], big))
+            tmax.append(reduce(mx, tc[t0:t0 + tb], -big))
+        wlo, whi = [], []
+        for k in range(nlev - 1):
+            pair = ~(np.isnan(c[k]) | np.isnan(c[k + 1]))
+            nolo, nohi = (F(np.nan), F(np.nan)) if through else (F(np.inf), F(-np.inf))
+            lo, hi = np.where(pair, np.fmin(c[k], c[k + 1]), nolo), np.where(pair, np.fmax(c[k], c[k + 1]), nohi)
+            a, b = reduce(mn, lo[None], big), reduce(mx, hi[None], -big)
+            if n % per_wave:  # the idle lanes of the last wave
+                a[-1], b[-1] = mn(a[-1], mn.reduce(lo[:v])), mx(b[-1], mx.reduce(hi[:v]))
+            wlo.append(a)
+            whi.append(b)
+        if mistake == "target reduction flushes subnormals":
+            tmin, tmax = [_flush(x) for x in tmin], [_flush(x) for x in tmax]
+        if mistake == "pair reduction flushes subnormals":
+            wlo, whi = [_flush(x) for x in wlo], [_flush(x) for x in whi]
+        allowed = np.zeros((nlev - 1, nt, n), bool)
+        skipped = 0
+        for k in range(nlev - 1):
+            for p in range(len(tmin)):
+                low = (wlo[k] < tmax[p]) if mistake == "strict on the low side" else (wlo[k] <= tmax[p])
+                high = (whi[k] > tmin[p]) if mistake == "strict on the high side" else (whi[k] >= tmin[p])
+                look = low & high
+                skipped += int((~look).sum())
+                allowed[k, p * tb:(p + 1) * tb] = np.repeat(look, per_wave)[:n]
+    return (lambda k, t: allowed[k, t]), skipped
 
 
 def hybrid_targets(ps_dst, alevel_dst, blevel_dst, undef=UNDEF):
